@@ -10,10 +10,21 @@ device synchronize on both sides and takes the max over ranks.
 Workload (configs[2] of BASELINE.json, the configuration the metric is quoted on):
   512^3 f32 synthetic volume (sum of 32 Gaussians + 0.05 value noise, seed 2024),
   1920x1080, camera r = 1.6 (frame-filling), TF-2 (demo ramp), gradient Phong shading +
-  early-ray termination (eps 1e-5).  The reference-semantics variant (no shading, no ERT) is
-  timed as well and reported under "variants".
+  early-ray termination (eps 1e-5).  With --full the reference-semantics variant (no shading,
+  no ERT) is timed as well and reported under "variants".
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W].
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full].
+  A plain run sets up, warms up, times the K steps and prints the result line: the headline
+  (`value`, `ms_per_step`, fps), the roofline of the timed kernel and the per-rank timings,
+  all from those K steps.
+  --dump-outputs DIR: after the timed steps, write the frame the last timed step produced (what
+        a caller of the frame path receives) as DIR/frame_rgba8.npy, float32 (H, W, 4) in 0..255.
+        The inputs are seeded, so two builds run with the same arguments compare frame for frame.
+  --full: everything else the benchmark measures or checks, each in runs of its own after the
+        headline: the variants (serial frames, default camera, reference semantics, skip-empty,
+        exact gradient, view switch, orbit, PCIe-inclusive host output; --no-variants drops
+        them), the CPU baseline (--no-cpu-baseline drops it), the reference-equivalent sample
+        count and, for N > 1, frame_check (assembled frame == single-GPU frame).
   N > 1 under torch.distributed.run (WORLD_SIZE set): one process per GPU, the library's RCCL
         frame path (vr_dist.h); WORLD_SIZE must equal N.
   N > 1 without WORLD_SIZE: bench.py starts `python -m torch.distributed.run --nproc-per-node N
@@ -200,7 +211,8 @@ class GroupFrames:
         self.stream.synchronize()
 
 
-def run_variant(rp, cfg, steps, warmup, rank, world, inflight, row_block=8, group=False):
+def run_variant(rp, cfg, steps, warmup, rank, world, inflight, row_block=8, group=False,
+                check_frame=True):
     """Time `steps` frames; returns a dict: secs (max over ranks), kms (this rank's average
     kernel ms), frame (frame work counters), mine (this rank's), shard_px, check (N > 1:
     assembled frame == single-rank frame) and per_rank timings.  For N > 1 a frame is: render
@@ -208,7 +220,9 @@ def run_variant(rp, cfg, steps, warmup, rank, world, inflight, row_block=8, grou
     frames are in flight (vr_dist.FramePipeline): frame i's work goes to stream i mod
     inflight, so consecutive frames overlap on the device and a frame's gather overlaps the
     next frames' renders; inflight = 1 is the serial frame loop.  group: rp is a multi-device
-    context (one process, vr_create_mask) that splits and gathers every frame itself."""
+    context (one process, vr_create_mask) that splits and gathers every frame itself.
+    check_frame=False leaves the N > 1 check out (check None).  `output` is the frame of the
+    last step as its caller receives it (int32 RGBA8 per pixel, H rows; rank 0)."""
     W, H = cfg["W"], cfg["H"]
     cam = synth.camera(cfg["cam"]).to_vr_camera()
     p = vr_amd.default_params(shading=cfg["shading"], ert_eps=cfg["ert"],
@@ -317,7 +331,7 @@ def run_variant(rp, cfg, steps, warmup, rank, world, inflight, row_block=8, grou
                                  assemble_span_ms=round(t["assemble_ms"] / n, 4) if m == 0 else None,
                                  frames=t["frames"]))
     check = None
-    if world > 1 and rank == 0:
+    if check_frame and world > 1 and rank == 0:
         # the assembled frame must equal this device's single-rank render of the whole frame
         full = torch.empty((vr_amd.shard_rows(H, row_block, 1), W), dtype=torch.int32, device="cuda")
         rp.render_device(cam, p, full.data_ptr(), vr_amd.OUT_RGBA8, row_block, 0, 1,
@@ -327,6 +341,8 @@ def run_variant(rp, cfg, steps, warmup, rank, world, inflight, row_block=8, grou
     return dict(secs=float(el.item()), kms=kms / max(nl, 1), frame=frame_stats, mine=my_stats,
                 shard_px=sr * W, check=check, per_rank=per_rank, warmup_frames=warmup,
                 last_frame=pipe.last.frame if group else None,
+                output=(pipe.last.shard[:H] if world == 1 and isinstance(pipe, vr_dist.FramePipeline)
+                        else pipe.last.frame),
                 last_frame_ptr=slots[0].shard.data_ptr() if slots else pipe.last.frame.data_ptr(),
                 keep=slots)
 
@@ -432,6 +448,25 @@ def orbit(rp, cfg, frame_ptr, n=360):
                     ms_per_frame=round(pip2, 4),
                     gsamples_per_s=round(float(samples.sum()) / (pip2 * 1e-3 * n) / 1e9, 3)),
                 memory_after=mem)
+
+
+DUMP_MAX_BYTES = 48 << 20  # per run, under the 64 MB a dump may take
+
+
+def dump_outputs(path, frame, H, W):
+    """--dump-outputs: the frame of the last timed step (int32 RGBA8 per pixel, on the device)
+    as path/frame_rgba8.npy, float32 (H, W, 4).  A frame above DUMP_MAX_BYTES as float32 is
+    written as a fixed sample of its pixels (seed 0): frame_rgba8.npy is then (n, 4) and
+    frame_rgba8_pixels.npy holds the n flat pixel indices (float64)."""
+    os.makedirs(path, exist_ok=True)
+    px = frame.contiguous().cpu().numpy().view(np.uint8).reshape(H * W, 4)
+    if px.size * 4 > DUMP_MAX_BYTES:
+        n = DUMP_MAX_BYTES // (4 * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        np.save(os.path.join(path, "frame_rgba8_pixels.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, "frame_rgba8.npy"), px[idx].astype(np.float32))
+    else:
+        np.save(os.path.join(path, "frame_rgba8.npy"), px.reshape(H, W, 4).astype(np.float32))
 
 
 def host_cores():
@@ -592,8 +627,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the variants, the CPU baseline, the "
+                         "reference-equivalent sample count and (N > 1) the frame check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's frame as DIR/frame_rgba8.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: no variants")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
     # 3 frames in flight on the box's 4 hardware queues: C3 318.9-326.4 Gsamples/s against
     # 309.6-312.2 with 4 and 317.8-322.3 with 6 (profiles/r03/frames_in_flight/)
@@ -690,16 +730,20 @@ def main():
     if BACKEND != "nccl":
         inflight = 1
     warm = max(args.warmup, STEADY_WARMUP)
+    with_variants = args.full and not args.no_variants
+    with_cpu = args.full and not args.no_cpu_baseline
 
     # also the reference-equivalent sample count (volume.frag as written: no
     # ERT, every in-slab step sampled) of the same frame, per second of this configuration
-    ref_cam = synth.camera(cfg["cam"]).to_vr_camera()
-    ref_stats = rp.count_work(ref_cam, vr_amd.default_params(), 8, rank, world)
-    ref_samples = torch.tensor([ref_stats["samples"]], dtype=torch.float64,
-                               device="cuda" if BACKEND == "nccl" else "cpu")
-    if world > 1:
-        dist.all_reduce(ref_samples, op=dist.ReduceOp.SUM)
-    ref_samples = int(ref_samples.item())
+    ref_samples = None
+    if args.full:
+        ref_cam = synth.camera(cfg["cam"]).to_vr_camera()
+        ref_stats = rp.count_work(ref_cam, vr_amd.default_params(), 8, rank, world)
+        ref_samples = torch.tensor([ref_stats["samples"]], dtype=torch.float64,
+                                   device="cuda" if BACKEND == "nccl" else "cpu")
+        if world > 1:
+            dist.all_reduce(ref_samples, op=dist.ReduceOp.SUM)
+        ref_samples = int(ref_samples.item())
 
     def frame_check(last_frame, vcfg, p):
         """Multi-device context: the assembled frame == a one-device context's frame, bytes."""
@@ -714,8 +758,11 @@ def main():
             one.close()
 
     # The headline first: W (at least STEADY_WARMUP) untimed frames, then exactly K timed ones.
-    R = run_variant(rp, cfg, args.steps, warm, rank, world, inflight, group=group)
-    if group and rank == 0:
+    R = run_variant(rp, cfg, args.steps, warm, rank, world, inflight, group=group,
+                    check_frame=args.full)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, R["output"], cfg["H"], cfg["W"])
+    if args.full and group and rank == 0:
         R["check"] = frame_check(R["last_frame"], cfg, vr_amd.default_params(
             shading=cfg["shading"], ert_eps=cfg["ert"], frames_in_flight=inflight))
     secs, kms, fstats = R["secs"], R["kms"], R["frame"]
@@ -733,7 +780,7 @@ def main():
 
     variants = {}
     serial_kms = None
-    if not args.no_variants and inflight > 1:
+    if with_variants and inflight > 1:
         # the serial form too (one frame at a time; for N > 1 each frame's
         # gather waited for before the next render).  Its kernels run alone on the device,
         # so their HIP-event durations are the kernel's own.
@@ -744,7 +791,7 @@ def main():
             value=round(V["frame"]["samples"] * ns / V["secs"] / 1e9, 3), unit="Gsamples/s",
             ms_per_step=round(V["secs"] / ns * 1e3, 4), fps=round(ns / V["secs"], 2),
             kernel_ms=round(V["kms"], 4), frame_check=V["check"], warmup_frames=V["warmup_frames"])
-    if not args.no_variants and args.config == "c3":
+    if with_variants and args.config == "c3":
         # the reference's default camera (benchmarks at r=1.6 plus the default)
         dcfg = CONFIGS["c3_default"]
         V = run_variant(rp, dcfg, args.steps, warm, rank, world, inflight, group=group)
@@ -800,7 +847,7 @@ def main():
                  "bit-identical to the f32 oracle",
             warmup_frames=V["warmup_frames"])
 
-    if not args.no_variants and args.config == "c3" and world == 1 and not group:
+    if with_variants and args.config == "c3" and world == 1 and not group:
         # A camera crossing view classes: after frames of the fill view (the
         # difference field), the reference's default camera needs the stencil copy (~0.76 GB for
         # 512^3).  Built lazily, inside its first frame; or ahead by vr_prepare.  Serial frames,
@@ -841,10 +888,10 @@ def main():
             note="host-timed serial frames around vr_render_device; vr_prepare builds the copy "
                  "outside the frame (vr.h ABI 7)")
 
-    if not args.no_variants and args.config == "c3" and world == 1 and not group:
+    if with_variants and args.config == "c3" and world == 1 and not group:
         variants["orbit"] = orbit(rp, cfg, R["last_frame_ptr"])
 
-    if not args.no_variants and world == 1 and not group:
+    if with_variants and world == 1 and not group:
         # PCIe-inclusive: vr_render into (pageable) host memory, the drop-in record() path.
         # The frame's RGBA8 bytes cross PCIe inside the timed region; row bands copy while
         # the later bands render (vr_api.hip vr_render).  Never the headline value.
@@ -867,7 +914,7 @@ def main():
     # launching thread of the GPU runs
     cpu = None
     small = int(np.prod(cfg["dims"])) <= 512 ** 3  # the oracle needs the volume as host floats
-    if rank == 0 and n_gpus == 1 and not args.no_cpu_baseline and small:
+    if rank == 0 and n_gpus == 1 and with_cpu and small:
         cpu = cpu_baseline(rp, cfg, args.cpu_budget)
         nproc = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else os.cpu_count()
         if nproc and nproc != cpu["cores"]:
@@ -912,7 +959,8 @@ def main():
             "warmup": args.warmup,
             "ms_per_step": round(frame_s * 1e3, 4),
             "fps": round(fps, 2),
-            "reference_equivalent_gsamples_per_s": round(ref_samples * args.steps / secs / 1e9, 3),
+            "reference_equivalent_gsamples_per_s": (round(ref_samples * args.steps / secs / 1e9, 3)
+                                                    if ref_samples is not None else None),  # --full
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -971,11 +1019,13 @@ def main():
             # derived structures (difference field, alternative copies, skip-empty) and the
             # budget that caps them (vr.h VR_MEMORY_BUDGET_DEFAULT: 5x the bricks)
             "memory_per_device": memory,
-            "frame_check": R["check"],  # N > 1: assembled frame == single-GPU frame, bit for bit
+            # --full, N > 1: assembled frame == single-GPU frame, bit for bit
+            "frame_check": R["check"],
             "per_rank": R["per_rank"],
             # N > 1 started by this script (launch_ranks): the launch path and the parent's
             # GPU-file check; null when the driver's launcher started the ranks itself
             "launch": json.loads(os.environ["VR_BENCH_LAUNCH"]) if os.environ.get("VR_BENCH_LAUNCH") else None,
+            "full": args.full,
             "variants": variants,
         }
         sys.stdout.flush()

@@ -80,7 +80,7 @@ def test_library_loads_and_pure_entry_points():
     assert L.vr_debug_timing_member(None, 0, None) == -22
 
 
-def test_struct_layouts_match_header():
+def test_struct_layouts_match_header(tmp_path):
     # sizes of the ABI structs as declared in vr.h (no padding surprises across the boundary)
     assert C.sizeof(vr_amd.vr_camera) == 4 * (16 + 3 + 3)
     assert C.sizeof(vr_amd.vr_params) == 4 * (3 + 1 + 4 + 3 + 1 + 6)
@@ -95,7 +95,7 @@ int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(
   sizeof(vr_stats), offsetof(vr_params, spec_power), offsetof(vr_params, skip_empty), offsetof(vr_params, frames_in_flight), offsetof(vr_params, exact_gradient), offsetof(vr_params, depth_zero_to_one),
   sizeof(vr_memory_info), sizeof(vr_member_timing), offsetof(vr_member_timing, kernel_ms)); return 0; }
 """
-    tmp = os.path.join("/tmp", "vr_abi_layout")
+    tmp = str(tmp_path / "vr_abi_layout")
     with open(tmp + ".c", "w") as f:
         f.write(test)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), tmp + ".c", "-o", tmp], check=True)

@@ -54,5 +54,37 @@ def test_launch_rehearsal_needs_two_ranks_and_a_device():
 
 
 def test_gpu_fds_sees_no_device_file_in_a_cpu_process():
+    """A process that has imported bench (torch, the library binding) and counted the devices,
+    but never initialised HIP, holds no GPU device file.  Checked in a fresh child: on a GPU
+    box the test process itself may have initialised HIP in an earlier test."""
+    code = ("import sys; sys.path.insert(0, %r); import bench, torch; torch.cuda.device_count(); "
+            "print(bench.gpu_fds())" % ROOT)
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert r.stdout.split("\n")[-2] == "[]", r.stdout
+
+
+def test_dump_outputs_writes_the_frame_or_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the size cap is written whole as float32 (H, W, 4); a
+    larger one as the same seeded pixel sample every time, with the sampled pixels' indices."""
+    import numpy as np
+    import torch
     import bench
-    assert bench.gpu_fds() == []
+    H, W = 6, 10
+    rgba = np.random.default_rng(5).integers(0, 256, (H, W, 4), dtype=np.uint8)
+    frame = torch.from_numpy(rgba.view(np.int32).reshape(H, W).copy())
+    bench.dump_outputs(str(tmp_path / "a"), frame, H, W)
+    assert sorted(os.listdir(tmp_path / "a")) == ["frame_rgba8.npy"]
+    f = np.load(tmp_path / "a" / "frame_rgba8.npy")
+    assert f.dtype == np.float32 and np.array_equal(f, rgba.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 24 * 7)
+    got = []
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame, H, W)
+        idx = np.load(tmp_path / d / "frame_rgba8_pixels.npy")
+        s = np.load(tmp_path / d / "frame_rgba8.npy")
+        assert idx.dtype == np.float64 and s.dtype == np.float32 and s.shape == (7, 4)
+        assert idx.nbytes + s.nbytes <= 24 * 7 and len(np.unique(idx)) == 7
+        assert np.array_equal(s, rgba.reshape(-1, 4)[idx.astype(np.int64)].astype(np.float32))
+        got.append(idx)
+    assert np.array_equal(got[0], got[1])

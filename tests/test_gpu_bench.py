@@ -13,14 +13,23 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_bench_prints_one_contract_line(gpu):
+def test_bench_prints_one_contract_line(gpu, tmp_path):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-variants"],
+                        "--no-cpu-baseline", "--no-variants", "--dump-outputs", str(tmp_path / "out")],
                        cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
+    # a plain run: the headline alone; what --full adds is absent from the line
+    assert d["full"] is False and d["variants"] == {} and d["cpu_baseline"] is None
+    # --dump-outputs: the last timed frame, float32 RGBA in 0..255 over the 1080p viewport
+    import numpy as np
+    assert sorted(os.listdir(tmp_path / "out")) == ["frame_rgba8.npy"]
+    f = np.load(tmp_path / "out" / "frame_rgba8.npy")
+    assert f.dtype == np.float32 and f.shape == (1080, 1920, 4)
+    assert f.min() >= 0 and f.max() <= 255 and np.array_equal(f, np.round(f))
+    assert len(np.unique(f[..., :3])) > 16  # a rendered frame, not a cleared buffer
     base = json.load(open(os.path.join(ROOT, "BASELINE.json")))
     assert d["metric"] == base["metric"]
     assert d["unit"] == "Gsamples/s" and d["higher_is_better"] is True
@@ -50,7 +59,7 @@ def test_bench_multi_device_context_path(gpu):
     one-GPU box: one contract line, n_gpus 1, and the assembled frame equals a one-device
     context's frame (frame_check)."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-variants", "--multi-device-context"],
+                        "--full", "--no-cpu-baseline", "--no-variants", "--multi-device-context"],
                        cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -66,7 +75,7 @@ def test_bench_member_rehearsal_on_one_gpu(gpu):
     exchange) under bench.py's frame loop; the assembled frame equals a one-device frame and
     the per-member rows name both members."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2",
-                        "--no-cpu-baseline", "--no-variants", "--members-on-one-gpu", "2"],
+                        "--full", "--no-cpu-baseline", "--no-variants", "--members-on-one-gpu", "2"],
                        cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -86,7 +95,8 @@ def test_bench_rehearses_the_driver_launch_path(gpu):
     rank 0's own whole-frame render, one per_rank row per rank, and the launching parent held
     no GPU device file when it spawned the ranks."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-launch",
-                        "--steps", "3", "--warmup", "0", "--no-cpu-baseline", "--no-variants"],
+                        "--steps", "3", "--warmup", "0", "--full", "--no-cpu-baseline",
+                        "--no-variants"],
                        cwd=ROOT, capture_output=True, text=True, timeout=170)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

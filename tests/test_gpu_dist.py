@@ -3,7 +3,7 @@ communicator, the only one a single device can hold.  Render -> ncclGather -> as
 stream-ordered over 1-3 frames in flight, and every assembled frame must equal the
 single-GPU render of the same camera byte for byte.  The multi-rank logic is the same code
 with nranks > 1; the CPU gloo tests (test_multirank.py) cover the row-block layout, and the
-driver's 8-GPU run checks it with bench.py's frame_check."""
+driver's 8-GPU run checks it with bench.py --full's frame_check."""
 import numpy as np
 import pytest
 

@@ -15,6 +15,16 @@ SRC = [os.path.join(ROOT, "volumetric-renderer_amd", "host", "vr_host.cpp"),
        os.path.join(ROOT, "tools", "host_sanitize", "nrrd_harness.cpp")]
 
 
+def _fixed_addresses():
+    """Run in the ThreadSanitizer child before it starts: address-space randomisation off for
+    that process alone (personality ADDR_NO_RANDOMIZE).  This TSan runtime accepts the program
+    and its libraries only in fixed address windows and ends with "FATAL: ThreadSanitizer:
+    unexpected memory mapping" before main() on kernels that randomise over more bits than the
+    windows span (vm.mmap_rnd_bits 32); newer runtimes re-execute themselves this way."""
+    import ctypes
+    ctypes.CDLL(None).personality(0x0040000)
+
+
 def build(tmp_path, flags, name):
     exe = str(tmp_path / name)
     r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", *flags, "-I", os.path.join(ROOT, "include"),
@@ -40,6 +50,7 @@ def test_host_code_under_sanitizers(tmp_path):
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0 and "runtime error" not in r.stderr, r.stderr[-3000:]
     exe = build(tmp_path, ["-fsanitize=thread"], "tsan")
-    r = subprocess.run([exe, str(big), str(bigf)], capture_output=True, text=True, env=env, timeout=300)
+    r = subprocess.run([exe, str(big), str(bigf)], capture_output=True, text=True, env=env, timeout=300,
+                       preexec_fn=_fixed_addresses)
     assert r.returncode == 0 and "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
     assert "loaded 2 of 2" in r.stdout

@@ -83,14 +83,14 @@ def test_frame_rendered_into_imported_memory(gpu, mask):
     assert "fd_open_after_release=1" in r.stdout  # the caller keeps the fd (vr.h)
 
 
-def test_shim_takes_the_clip_form_from_glms_configuration():
+def test_shim_takes_the_clip_form_from_glms_configuration(tmp_path):
     """vr_params.depth_zero_to_one (ABI 8) in the shim: glm's GLM_CONFIG_CLIP_CONTROL (fixed at
     glm's first include) selects it; without glm, or in glm's default [-1, 1] form, it is 0 --
     the reference's build (offscreen_pass.cpp:3 defines GLM_FORCE_DEPTH_ZERO_TO_ONE after glm
     came in through offscreen_pass.h:3).  glm is an un-vendored submodule of the reference, so
     its setup.hpp macros are stated here as glm >= 0.9.9 defines them."""
-    src = os.path.join("/tmp", "vr_shim_clip.cpp")
-    exe = os.path.join("/tmp", "vr_shim_clip")
+    src = str(tmp_path / "vr_shim_clip.cpp")
+    exe = str(tmp_path / "vr_shim_clip")
     body = r"""
 #include <vr/offscreen_pass_hip.hpp>
 #include <cstdio>

@@ -14,7 +14,7 @@ for r in 1 2 3; do
   done
 done
 for b in lib lib_d0; do
-  VR_AMD_LIB=$PWD/volumetric-renderer_amd/$b/libvr_amd.so timeout -k 10 200 python -u bench.py --config c3 --steps 20 --warmup 5 --no-cpu-baseline > $O/full_${b}.json 2> $O/full_${b}.err || exit 1
+  VR_AMD_LIB=$PWD/volumetric-renderer_amd/$b/libvr_amd.so timeout -k 10 200 python -u bench.py --full --config c3 --steps 20 --warmup 5 --no-cpu-baseline > $O/full_${b}.json 2> $O/full_${b}.err || exit 1
   python - $O/full_${b}.json $b <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1])); v=d.get('variants',{})

@@ -9,7 +9,7 @@ timeout -k 10 480 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-me
 rc=$?; tail -3 $O/pytest.log; [ $rc -le 1 ] || exit $rc
 bash tools/measure_round.sh r05_final "c3 c3_default c3_ref c2 c4 c5" || exit $?
 for m in 2 3 8; do
-  timeout -k 10 200 python -u bench.py --members-on-one-gpu $m --no-variants --no-cpu-baseline --steps 40 --warmup 10 > $O/bench_members$m.json 2> $O/bench_members$m.err || exit 1
+  timeout -k 10 200 python -u bench.py --full --members-on-one-gpu $m --no-variants --no-cpu-baseline --steps 40 --warmup 10 > $O/bench_members$m.json 2> $O/bench_members$m.err || exit 1
   python -c "import json; d=json.load(open('$O/bench_members$m.json')); print('members', $m, d['value'], d['ms_per_step'], d['frame_check'], [ (r['rank'], r['kernel_ms'], r['render_span_ms'], r['gather_span_ms']) for r in d['per_rank']])"
 done
 for cfg in c2 c4 c5; do

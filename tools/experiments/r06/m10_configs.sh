@@ -9,7 +9,7 @@ for r in 1 2; do
   done
 done
 for c in c2 c4 c5; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline --steps 40 --warmup 5 > $O/bench_$c.json 2> $O/bench_$c.err || exit $?
+  timeout -k 10 300 python bench.py --full --config $c --no-cpu-baseline --steps 40 --warmup 5 > $O/bench_$c.json 2> $O/bench_$c.err || exit $?
 done
-timeout -k 10 400 python bench.py --gpus 2 --rehearse-launch --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_rehearse_launch2.json 2> $O/bench_rehearse_launch2.err || exit $?
-timeout -k 10 300 python bench.py --members-on-one-gpu 3 --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $O/bench_members3.json 2> $O/bench_members3.err
+timeout -k 10 400 python bench.py --full --gpus 2 --rehearse-launch --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_rehearse_launch2.json 2> $O/bench_rehearse_launch2.err || exit $?
+timeout -k 10 300 python bench.py --full --members-on-one-gpu 3 --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $O/bench_members3.json 2> $O/bench_members3.err

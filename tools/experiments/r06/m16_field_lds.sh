@@ -9,4 +9,4 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 400 --timeout-method threa
     tests/test_gpu_parity.py tests/test_gpu_round4.py tests/test_gpu_round6.py tests/test_gpu_inputs.py \
     "tests/test_gpu_fullsize.py::test_c3_512_f32_1080p_whole_frame" > $O/pytest.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/trace -o run --output-format csv \
-    -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 3 > $O/trace.log 2>&1
+    -- python3 bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $O/trace.log 2>&1
