@@ -56,6 +56,7 @@
 #include <vector>
 
 #include "vr.h"
+#include "vr_modes.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -222,6 +223,17 @@ class BasicOffscreenPass {
     void transfer_function_changed(const std::vector<uint32_t> &data)  // :279-288
     {
         check(vr_set_transfer_function(ctx_, data.data(), (uint32_t)data.size()));
+    }
+
+    // Extension (vr_modes.h): VR_MODE_COMPOSITE, the reference's composite, or VR_MODE_MIP,
+    // maximum-intensity projection, for the frames recorded from now on (a UI toggle calls it
+    // like slicing_changed)
+    void render_mode_changed(int mode) { check(vr_set_render_mode(ctx_, mode)); }
+    int render_mode() const
+    {
+        int m = VR_MODE_COMPOSITE;
+        vr_get_render_mode(ctx_, &m);
+        return m;
     }
 
     // offscreen_pass.h:53-54: the presenter's sampler / view of the frame's image

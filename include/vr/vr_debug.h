@@ -35,13 +35,15 @@ enum vr_knob {
     VR_KNOB_NARROW = 8,     /* 1 (default): 32/64-bit uploads whose voxels are all integers
                                that fit 8/16 bits are stored in that type (same frames); 0:
                                keep f32 storage (next upload)                              */
-    VR_KNOB_ALT_GEOMETRY = 9 /* f32 volumes: -1 auto (oblique views and rays along x read a
+    VR_KNOB_ALT_GEOMETRY = 9, /* f32 volumes: -1 auto (oblique views and rays along x read a
                                7x15x8-cell-brick copy; sparse views along the bricks' rows the
                                stencil copy when shaded, a plain one-voxel-per-element 15^3
                                one when not), 0 never, 1 the
                                oblique copy, 3 the plain copy, 4 the stencil copy (29^3-cell
                                plain bricks with a 1-below / 2-above apron), whenever the
                                launch allows it (2, the retired z-pair sparse copy: EINVAL) */
+    VR_KNOB_MIP_INFLIGHT = 10 /* VR_MODE_MIP (vr_modes.h): samples of a ray whose loads are in
+                               flight together: 0 auto, 1, 2 or 4 (same bytes)             */
 };
 
 /* Per-device timing of a context (ABI 7), so that a multi-GPU frame that runs slow names its

@@ -8,6 +8,7 @@
 // become negative status codes with a message in vr_last_error().
 #include "../../include/vr/vr.h"
 #include "../../include/vr/vr_debug.h"
+#include "../../include/vr/vr_modes.h"
 #include "vr_internal.h"
 #include "vr_group.h"
 
@@ -66,6 +67,7 @@ struct vr_ctx {
     uint32_t *tf_nz = nullptr;  // prefix count of nonzero-alpha texels (tf_n + 1)
     float smin[3] = {0.0f, 0.0f, 0.0f};
     float smax[3] = {1.0f, 1.0f, 1.0f};
+    int render_mode = VR_MODE_COMPOSITE;  // vr_modes.h: context state, like the slice box
     // empty-space classification (skip_empty), built lazily: per-brick value range after a
     // volume change, the brick distance field after a volume or TF change
     float2 *brick_range = nullptr;
@@ -142,7 +144,7 @@ struct vr_ctx {
     // product path never reads the process environment
     struct Knobs {
         int pipeline = -1, pair = -1, pair_lanes = 0, grad_field = -1, u8_layout = -1,
-            tile_order = 0, narrow = 1, alt = -1;
+            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0;
     } knobs;
     // multi-device context (vr_create_mask): one member context per device of the mask, the
     // volume/TF/slicing replicated on each, frames rendered across them by `group`
@@ -926,11 +928,11 @@ void free_derived(vr_ctx *c)
     (void)hipStreamSynchronize(nullptr);
 }
 
-// skip_empty: (re)build the per-brick ranges and the distance field when stale, on `s` ahead of
-// the march that reads them.
-int ensure_skip(vr_ctx *c, MarchParams &P, hipStream_t s)
+// The skip-empty classification's buffers for the current brick grid (per-brick ranges, plus the
+// entry of launch_range_max; distance field + scratch).  *have = false: over the memory budget.
+int alloc_skip(vr_ctx *c, size_t nb, bool *have)
 {
-    const size_t nb = (size_t)bricks_for(c->nx, 0, c->layout) * bricks_for(c->ny, 1, c->layout) * bricks_for(c->nz, 2, c->layout);
+    *have = false;
     if (nb > 0xFFFFFFFFull) return fail(c, VR_EINVAL, "skip_empty: too many bricks");
     if (c->nbricks_alloc != nb && !budget_allows(c, nb * kSkipBytesPerBrick, c->nbricks_alloc * kSkipBytesPerBrick))
         return VR_OK;  // over the memory budget: the frame samples every step (same pixels)
@@ -941,18 +943,40 @@ int ensure_skip(vr_ctx *c, MarchParams &P, hipStream_t s)
         c->skip_dist = nullptr;
         c->nbricks_alloc = 0;
         c->range_valid = c->dist_valid = false;
-        HIP_TRY(c, hipMalloc(&c->brick_range, nb * sizeof(float2)), "hipMalloc(brick ranges)");
+        HIP_TRY(c, hipMalloc(&c->brick_range, (nb + 1) * sizeof(float2)), "hipMalloc(brick ranges)");
         HIP_TRY(c, hipMalloc(&c->skip_dist, 2 * nb), "hipMalloc(skip distance field)");
         c->nbricks_alloc = nb;
     }
+    *have = true;
+    return VR_OK;
+}
+// The per-brick value ranges of the current volume, on `s` (stale after a volume change only).
+int build_ranges(vr_ctx *c, size_t nb, hipStream_t s)
+{
+    if (c->range_valid) return VR_OK;
+    HIP_TRY(c, launch_brick_range(c->layout, c->bricks, bricks_for(c->nx, 0, c->layout), bricks_for(c->ny, 1, c->layout),
+                                  bricks_for(c->nz, 2, c->layout), c->brick_range, s),
+            "brick range kernel");
+    HIP_TRY(c, launch_range_max(c->brick_range, (uint32_t)nb, s), "brick range maximum kernel");
+    c->range_valid = true;
+    c->dist_valid = false;
+    return VR_OK;
+}
+size_t brick_count(const vr_ctx *c)
+{
+    return (size_t)bricks_for(c->nx, 0, c->layout) * bricks_for(c->ny, 1, c->layout) * bricks_for(c->nz, 2, c->layout);
+}
+
+// skip_empty: (re)build the per-brick ranges and the distance field when stale, on `s` ahead of
+// the march that reads them.
+int ensure_skip(vr_ctx *c, MarchParams &P, hipStream_t s)
+{
+    const size_t nb = brick_count(c);
+    bool have = false;
+    if (int rc = alloc_skip(c, nb, &have)) return rc;
+    if (!have) return VR_OK;
     if (!c->range_valid || !c->dist_valid) ++c->n_builds;
-    if (!c->range_valid) {
-        HIP_TRY(c, launch_brick_range(c->layout, c->bricks, bricks_for(c->nx, 0, c->layout), bricks_for(c->ny, 1, c->layout),
-                                      bricks_for(c->nz, 2, c->layout), c->brick_range, s),
-                "brick range kernel");
-        c->range_valid = true;
-        c->dist_valid = false;
-    }
+    if (int rc = build_ranges(c, nb, s)) return rc;
     if (!c->dist_valid) {
         HIP_TRY(c, launch_skip_dist(c->brick_range, bricks_for(c->nx, 0, c->layout), bricks_for(c->ny, 1, c->layout),
                                     bricks_for(c->nz, 2, c->layout), c->tf_nz, (int)c->tf_n, c->vmin,
@@ -961,6 +985,22 @@ int ensure_skip(vr_ctx *c, MarchParams &P, hipStream_t s)
         c->dist_valid = true;
     }
     P.skip_dist = c->skip_dist;
+    P.skip_empty = 1;
+    return VR_OK;
+}
+
+// MIP range skipping: the ranges alone (no TF-dependent distance field: a TF change invalidates
+// nothing here), within the memory budget as ensure_skip.
+int ensure_mip_ranges(vr_ctx *c, MarchParams &P, MipArgs &M, hipStream_t s)
+{
+    const size_t nb = brick_count(c);
+    bool have = false;
+    if (int rc = alloc_skip(c, nb, &have)) return rc;
+    if (!have) return VR_OK;
+    if (!c->range_valid) ++c->n_builds;
+    if (int rc = build_ranges(c, nb, s)) return rc;
+    M.brick_range = c->brick_range;
+    M.nbricks = (uint32_t)nb;
     P.skip_empty = 1;
     return VR_OK;
 }
@@ -1033,7 +1073,7 @@ bool ensure_grad(vr_ctx *c, MarchParams &P, hipStream_t s, bool half, bool *refu
 // previous record, the new record also covers every earlier build, on whichever stream it ran
 // (a frame that reads a field built on one stream and builds another on its own, e.g. a
 // shaded skip-empty frame, or a later frame reading both).
-int ensure_derived(vr_ctx *c, const vr_params *p, MarchParams &P, hipStream_t s, uint32_t *refused)
+int wait_builds(vr_ctx *c, hipStream_t s)
 {
     if (c->built_recorded) {  // once per stream and build record (a wait costs ~3.7 us of host time)
         vr_ctx::Fence *f = fence_of(c, s);
@@ -1042,6 +1082,11 @@ int ensure_derived(vr_ctx *c, const vr_params *p, MarchParams &P, hipStream_t s,
             if (f) f->build_seen = c->build_gen;
         }
     }
+    return VR_OK;
+}
+int ensure_derived(vr_ctx *c, const vr_params *p, MarchParams &P, hipStream_t s, uint32_t *refused)
+{
+    if (int rc = wait_builds(c, s)) return rc;
     const bool r0 = c->range_valid, d0 = c->dist_valid;
     if (p->skip_empty) {
         int rc = ensure_skip(c, P, s);
@@ -1055,6 +1100,40 @@ int ensure_derived(vr_ctx *c, const vr_params *p, MarchParams &P, hipStream_t s,
     const bool built = (!r0 && c->range_valid) || (!d0 && c->dist_valid) || g_built;
     if (built) return record_build(c, s);
     return VR_OK;
+}
+
+// MIP frames (vr_modes.h) read the base bricks and, with skip_empty, the brick ranges: no
+// difference field, no lane groups, no alternative copy.  Builds are chained as ensure_derived's.
+int ensure_mip(vr_ctx *c, const vr_params *p, MarchParams &P, MipArgs &M, hipStream_t s,
+               uint32_t *refused)
+{
+    if (int rc = wait_builds(c, s)) return rc;
+    M.brick_range = nullptr;
+    M.nbricks = 0;
+    P.pipelined = 0;
+    if (!p->skip_empty) return VR_OK;
+    const bool r0 = c->range_valid;
+    if (int rc = ensure_mip_ranges(c, P, M, s)) return rc;
+    if (!P.skip_empty) *refused = VR_DERIVED_SKIP;
+    if (!r0 && c->range_valid) return record_build(c, s);
+    return VR_OK;
+}
+// Samples of a ray the MIP kernel keeps in flight (knob VR_KNOB_MIP_INFLIGHT overrides), by
+// measurement (tools/mip_bench.py, profiles/r07/mip/; ms per frame, K = 1 / 2 / 4):
+//   8-bit yz-quads (C2): 2 without skipping (fill 0.302 / 0.261 / 0.268, default camera 0.117 /
+//     0.094 / 0.105), 4 with (0.327 / 0.290 / 0.279 and 0.134 / 0.114 / 0.109);
+//   plain 8-bit bricks (C4): 2 (fill 1.19 / 1.04 / 1.02, with skipping 1.47 / 1.24 / 1.49);
+//   f32 (C3): 2 (fill 0.397 / 0.363 / 0.375, with skipping 0.448 / 0.405 / 0.463), but on sparse
+//     views (more than kAltSpan voxels per pixel step: the default camera) 1 without skipping
+//     (0.263 / 0.292 / 0.312: more loads in flight lose there; why was not measured) and 4 with
+//     (0.256 / 0.224 / 0.210);
+//   16-bit yz-quads: 2 (not measured).
+int mip_inflight(const vr_ctx *c, bool skip)
+{
+    if (c->knobs.mip_inflight) return c->knobs.mip_inflight;
+    if (c->layout == ST_F32 && c->pixel_span > kAltSpan) return skip ? 4 : 1;
+    if ((c->layout & kQuadFlag) && skip) return 4;
+    return kMipDefaultInFlight;
 }
 
 // f32 frames of oblique views (the centre ray's direction less than kAltAlign along every axis)
@@ -1333,6 +1412,7 @@ int *knob_slot(vr_ctx *c, int knob)
         case VR_KNOB_TILE_ORDER: return &c->knobs.tile_order;
         case VR_KNOB_NARROW: return &c->knobs.narrow;
         case VR_KNOB_ALT_GEOMETRY: return &c->knobs.alt;
+        case VR_KNOB_MIP_INFLIGHT: return &c->knobs.mip_inflight;
         default: return nullptr;
     }
 }
@@ -1344,6 +1424,7 @@ bool knob_value_ok(int knob, int v)
         case VR_KNOB_NARROW: return v == 0 || v == 1;
         case VR_KNOB_ALT_GEOMETRY: return v >= -1 && v <= 4 && v != 2;
         case VR_KNOB_TILE_ORDER: return v >= 0 && v <= 4;
+        case VR_KNOB_MIP_INFLIGHT: return v == 0 || v == 1 || v == 2 || v == 4;
         default: return v >= -1 && v <= 1;
     }
 }
@@ -1939,6 +2020,27 @@ int vr_set_slicing(vr_ctx *c, const float min_slice[3], const float max_slice[3]
     return VR_OK;
 }
 
+int vr_set_render_mode(vr_ctx *c, int mode)
+{
+    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
+    if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP)
+        return fail(c, VR_EINVAL, "unknown render mode");
+    if (is_group(c)) {  // frames already issued keep the old mode (as the slice box)
+        if (int rc = group_idle(c)) return rc;
+        for (vr_ctx *m : c->members)
+            if (int rc = vr_set_render_mode(m, mode)) return member_rc(c, m, rc);
+    }
+    c->render_mode = mode;
+    return VR_OK;
+}
+
+int vr_get_render_mode(const vr_ctx *c, int *mode)
+{
+    if (!c || !mode) return fail(nullptr, VR_EINVAL, "NULL argument");
+    *mode = c->render_mode;
+    return VR_OK;
+}
+
 uint32_t vr_shard_rows(uint32_t height, uint32_t row_block, uint32_t nranks)
 {
     if (row_block == 0 || nranks == 0) return 0;
@@ -2067,6 +2169,38 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
     hipStream_t s = static_cast<hipStream_t>(stream);
     ++c->frame_no;
     uint32_t refused = 0;  // VR_DERIVED_* the budget or free memory refused this frame
+    if (c->render_mode == VR_MODE_MIP) {
+        MipArgs M;
+        rc = ensure_mip(c, p, P, M, s, &refused);
+        if (rc) return rc;
+        if (!launch) return VR_OK;
+        if (refused) {
+            ++c->n_downgrades;
+            c->last_downgrade = refused;
+        }
+        const int K = mip_inflight(c, P.skip_empty != 0);
+        vr_ctx::TileSched *ts = tile_sched(c, P, stream, 0x40000000u | (P.skip_empty ? 2u : 0u) |
+                                                            ((uint32_t)K << 2) | ((uint32_t)c->layout << 8));
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        const bool timing = c->timing;
+        if (timing) {
+            e0 = pooled_event(c);
+            e1 = pooled_event(c);
+            if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
+            HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
+        }
+        HIP_TRY(c, launch_mip(c->layout, false, K, P, M, s), "mip kernel launch");
+        if (timing) {
+            HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
+            c->ev_pending.emplace_back(e0, e1);
+        }
+        if (ts && ts->launches++ % kReorderEvery == 0) {
+            HIP_TRY(c, launch_order_tiles(ts->cost, ts->lists, ts->perm, ts->per_xcd, s),
+                    "tile order kernel");
+            ts->have_perm = true;
+        }
+        return fence_record(c, s);
+    }
     rc = ensure_derived(c, p, P, s, &refused);
     if (rc) return rc;
     if (use_pair(c, P, p)) {  // L lanes per ray on 16 x (16 / L) tiles (march_pair_kernel)
@@ -2311,10 +2445,15 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
                           c->share, P);
     if (rc) return rc;
     uint32_t refused = 0;  // a count is not a frame: not a downgrade
-    rc = ensure_derived(c, p, P, nullptr, &refused);
+    MipArgs M;
+    const bool mip = c->render_mode == VR_MODE_MIP;
+    rc = mip ? ensure_mip(c, p, P, M, nullptr, &refused) : ensure_derived(c, p, P, nullptr, &refused);
     if (rc) return rc;
     HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
-    HIP_TRY(c, launch_march(c->layout, p->shading != 0, true, P, nullptr), "march (count) launch");
+    if (mip)
+        HIP_TRY(c, launch_mip(c->layout, true, 1, P, M, nullptr), "mip (count) launch");
+    else
+        HIP_TRY(c, launch_march(c->layout, p->shading != 0, true, P, nullptr), "march (count) launch");
     unsigned long long h[5];
     HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
     out->rays = h[0];
@@ -2451,6 +2590,12 @@ const char *vr_kernel_name(const vr_ctx *c, const vr_params *p)
 {
     if (!c) return "";
     if (is_group(c)) return vr_kernel_name(c->members[0], p);
+    if (c->render_mode == VR_MODE_MIP) {  // range skipping once the ranges are in place
+        thread_local std::string name;
+        const bool skip = p && p->skip_empty && c->range_valid && c->nbricks_alloc;
+        name = mip_kernel_name(c->layout, false, skip, mip_inflight(c, skip));  // of the last view
+        return name.c_str();
+    }
     // the variant the next vr_render_device launches (after a shaded frame built the field)
     const bool gf = p && p->shading && use_grad_field(c, p->exact_gradient == 0) && c->grad &&
                     c->grad_valid;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <cmath>
+#include <string>
 #include <type_traits>
 
 namespace vr {
@@ -365,6 +366,24 @@ struct MarchParams {
 hipError_t launch_march(int storage, bool shade, bool count, const MarchParams &p,
                         hipStream_t stream);
 const char *march_kernel_name(int storage, bool shade, bool count, bool skip, bool gf, bool pipe);
+// ---- Maximum-intensity projection (include/vr/vr_modes.h, mip_kernel) ----
+// What the MIP kernel reads beside MarchParams (a kernel argument of its own: MarchParams'
+// size is part of the composite kernels' descriptors, which the committed roofline data is
+// keyed on).  brick_range: per brick (index as skip_dist) {lo, hi} of every value a sample in
+// the brick can read, NaN bricks {NaN, NaN}, and one more entry after the last brick whose .y
+// is the largest hi of all (launch_range_max); null without range skipping.
+struct MipArgs {
+    const float2 *brick_range;
+    uint32_t nbricks;
+};
+// K: samples of a ray in flight (1, 2 or 4).  The layout is a base one (no alternative f32
+// copy); skip follows p.skip_empty (then m.brick_range is set).
+hipError_t launch_mip(int storage, bool count, int K, const MarchParams &p, const MipArgs &m,
+                      hipStream_t stream);
+std::string mip_kernel_name(int storage, bool count, bool skip, int K);
+constexpr int kMipDefaultInFlight = 2;
+// range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
+hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);
 // Wavefront count below which a launch uses the pipelined kernel (see build_params).
 constexpr uint32_t kPipelineMaxWaves = 24576;  // between N = 2 (16 K) and N = 1 (33 K) at 1080p
 constexpr size_t kPipelineMinBytes = 4ull << 30;  // large volumes: always pipelined

@@ -1396,6 +1396,220 @@ __global__ __launch_bounds__(kThreadsPerTile, (kMarchMinWaves<COUNT, SKIP, GF, P
 #endif
 }
 
+// ---- maximum-intensity projection (include/vr/vr_modes.h) ------------------------------------
+// The same ray as march_strip (pixel_ray, nsteps, the f32 position update, the bounds break and
+// the strict slab test), but a pixel keeps the largest trilinear sample m of its ray and reads
+// the TF once, at m: one composite step from T = 1 over the clear colour.  fmaxf is exact and
+// commutative and ignores a NaN operand, so the order the samples are taken in, and which of
+// them are proven not to exceed the running maximum and left out, never shows in the frame.
+// There is no dependent chain between samples: K steps' loads are issued before any of them is
+// filtered (lanes whose ray has ended, or whose sample is off-slab or skipped, load element 0
+// of the volume, one cached line, so the loads stay unconditional).
+//
+// SKIP: a sample whose brick's stored maximum hi (brick_range_kernel: every value a sample in
+// the brick can read, apron and zero border included) is not above the ray's running maximum
+// is not fetched.  Exact: a sample is three levels of fmaf(w, b - a, a) with w in [0, 1].  For
+// 8/16-bit voxels b - a is exact, so each level is the correctly rounded value of a point
+// between a and b and cannot pass max(a, b): tri <= hi.  For f32 voxels b - a rounds, and with
+// w = 1 (u - floor(u) rounds up to 1 just below a voxel centre) a level can pass max(a, b) by
+// an ulp of the larger operand, so hi is widened by the classifier's margin (classify_kernel,
+// 4e-6 (|lo| + |hi|), three orders above the three roundings; infinite when b - a can
+// overflow).  !(hi <= m) keeps NaN bricks.  The test reads m as it stood before the batch of K
+// steps: any earlier value of the maximum proves the same.  A ray of an 8/16-bit volume ends
+// once m reaches the largest hi of the volume.
+// COUNT: walks every step, fetches and skips per lane, and fills vr_stats (shaded 0).
+template <typename VT>
+constexpr bool kMipQuadRaw = !kZPair<VT> && !kPlainByte<VT>;
+template <typename VT, typename = void>
+struct MipRaw {
+    CellRaw<VT> w;
+    __device__ __forceinline__ void issue(const char *__restrict__ base, size_t e)
+    {
+        Cell8<VT>::issue(w, base, e);
+    }
+    __device__ __forceinline__ void decode(Cell8<VT> &c) const { c.decode(w); }
+};
+// yz-quad elements: the loaded words, decoded at consume (as CellRaw's z-pair and byte forms)
+template <typename VT>
+struct MipRaw<VT, std::enable_if_t<kMipQuadRaw<VT>>> {
+    uint32_t w[2 * kQuadWords<VT>];
+    __device__ __forceinline__ void issue(const char *__restrict__ base, size_t e)
+    {
+        quad_load2<VT>(base, e, w);
+    }
+    __device__ __forceinline__ void decode(Cell8<VT> &c) const
+    {
+        constexpr int QW = kQuadWords<VT>;
+        c.v[0] = qc<VT>(w, 0);
+        c.v[4] = qc<VT>(w, 1);
+        c.v[2] = qc<VT>(w, 2);
+        c.v[6] = qc<VT>(w, 3);
+        c.v[1] = qc<VT>(w + QW, 0);
+        c.v[5] = qc<VT>(w + QW, 1);
+        c.v[3] = qc<VT>(w + QW, 2);
+        c.v[7] = qc<VT>(w + QW, 3);
+    }
+};
+
+template <typename VT, bool COUNT, bool SKIP, int K>
+__device__ __forceinline__ void mip_strip(const MarchParams &P, const MipArgs &M, uint32_t tile_x,
+                                          uint32_t tile_y, uint32_t wave, uint32_t lane)
+{
+    using G = GeomOf<VT>;
+    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
+    const uint32_t wpr = kTile >> ws;
+    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
+    const uint32_t px = tile_x * kTile + (wave % wpr) * ww + lx_;
+    const uint32_t ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
+    bool active = px < P.W && ly < P.local_rows;
+    const uint32_t blk = ly / P.row_block;
+    const uint32_t gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) *
+                            P.row_block + (ly - blk * P.row_block);
+    active = active && gy < P.H;
+
+    float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
+    const bool covered = active && pixel_ray(P, px, gy, tex, dir);
+
+    float m = -INFINITY;
+    bool any = false;
+    unsigned long long n_samples = 0, n_steps = 0, n_skipped = 0;
+    uint32_t cur_brick = 0xFFFFFFFFu;
+    float cur_hi = INFINITY;
+    const char *__restrict__ vol = static_cast<const char *>(P.vol);
+    const int nsteps = covered ? P.nsteps : 0;
+    float p0 = tex[0], p1 = tex[1], p2 = tex[2];
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
+    float end_at = INFINITY;  // 8/16-bit volumes: no sample exceeds the largest brick maximum
+    if constexpr (SKIP && !COUNT && !kZPair<VT>) end_at = M.brick_range[M.nbricks].y;
+
+    struct Stage {
+        MipRaw<VT> r;
+        float ax, ay, az;
+        bool fetch, issued;
+    };
+    bool live = nsteps > 0;
+    for (int it = 0; live; it += K) {
+        Stage S[K];
+        const float m_in = m;
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const int k = it + s;
+            const bool interior = (unsigned)(k - 1) < (unsigned)kin;
+            // volume.frag:34-37: the first position outside ends the ray
+            live = live && k < nsteps &&
+                   (interior || !(p0 > 1.0f || p1 > 1.0f || p2 > 1.0f || p0 < 0.0f || p1 < 0.0f ||
+                                  p2 < 0.0f));
+            if (COUNT && live) ++n_steps;
+            // volume.frag:39-40 (strict)
+            const bool slab = live && (interior || (p0 < P.smax[0] && p1 < P.smax[1] &&
+                                                    p2 < P.smax[2] && p0 > P.smin[0] &&
+                                                    p1 > P.smin[1] && p2 > P.smin[2]));
+            int i, j, kk;
+            texel_coord(p0, P.fnx, i, S[s].ax);
+            texel_coord(p1, P.fny, j, S[s].ay);
+            texel_coord(p2, P.fnz, kk, S[s].az);
+            const int pi = i + kPad, pj = j + kPad, pk = kk + kPad;
+            bool fetch = slab;
+            if constexpr (SKIP) {
+                if (slab) {
+                    const uint32_t bb = ((uint32_t)pk / G::BZ * P.nby + (uint32_t)pj / G::BY) * P.nbx +
+                                        (uint32_t)pi / G::BX;
+                    if (bb != cur_brick) {
+                        cur_brick = bb;
+                        const float2 r = VR_OOB(7, bb, M.nbricks) ? make_float2(NAN, NAN)
+                                                                   : M.brick_range[bb];
+                        cur_hi = kZPair<VT> ? r.y + (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.y;
+                    }
+                    fetch = !(cur_hi <= m_in);
+                }
+            }
+            if (COUNT && slab) {
+                if (fetch)
+                    ++n_samples;
+                else
+                    ++n_skipped;
+            }
+            any = any || slab;
+            S[s].fetch = fetch;
+            size_t ce = fetch ? cell_offset<VT>(pi, pj, pk, P.nbx, P.nby) : (size_t)0;
+            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+            // without SKIP every step loads; with it a step no lane of the wave fetches does not
+            S[s].issued = !SKIP || __any(fetch);
+            if (S[s].issued) S[s].r.issue(vol, ce);
+            // volume.frag:47
+            p0 = p0 + d0 * P.step;
+            p1 = p1 + d1 * P.step;
+            p2 = p2 + d2 * P.step;
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            if (S[s].issued) {
+                Cell8<VT> c;
+                S[s].r.decode(c);
+                const float d = c.tri(S[s].ax, S[s].ay, S[s].az);
+                if (S[s].fetch) m = fmaxf(m, d);  // a NaN sample leaves m
+            }
+        }
+        if (!COUNT && m >= end_at) live = false;
+    }
+
+    if (COUNT) {
+        const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
+        const unsigned long long sm = wave_sum(n_samples);
+        const unsigned long long st = wave_sum(n_steps);
+        const unsigned long long sk = wave_sum(n_skipped);
+        if (lane == 0) {
+            atomicAdd(&P.counters[0], rays);
+            atomicAdd(&P.counters[1], sm);
+            atomicAdd(&P.counters[3], st);
+            atomicAdd(&P.counters[4], sk);
+        }
+    }
+    if (!active) return;
+
+    // one composite step from T = 1 (volume.frag:42-45), then the blend over the clear colour
+    float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    if (any) {
+        const float tt = div_by_range(m - P.vmin, P);
+        const float4 s = tf_lookup(P.tf, P.tf_n, P.tf_nf, tt);
+        cr = (s.x * s.w) * 1.0f;
+        cg = (s.y * s.w) * 1.0f;
+        cb = (s.z * s.w) * 1.0f;
+        T = 1.0f * (1.0f - s.w);
+    }
+    const float A = 1.0f - T;
+    const float omA = 1.0f - A;
+    const float o0 = cr * A + P.clear[0] * omA;
+    const float o1 = cg * A + P.clear[1] * omA;
+    const float o2 = cb * A + P.clear[2] * omA;
+    const float o3 = A * A + P.clear[3] * omA;
+    const size_t idx = (size_t)ly * P.W + px;
+    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
+    if (P.out_format == 0) {
+        static_cast<uint32_t *>(P.out)[idx] =
+            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
+    } else {
+        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
+    }
+}
+
+template <typename VT, bool COUNT, bool SKIP, int K>
+__global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams P, const MipArgs M)
+{
+    const int tid = threadIdx.x;
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    const long long wg_start = wall_clock64();
+    mip_strip<VT, COUNT, SKIP, K>(P, M, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
+        __syncthreads();
+        if (tid == 0)
+            P.tile_cost[tile_y * P.tiles_x + tile_x] =
+                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
+    }
+}
+
 // ---- lane-pair march (small launches) ----------------------------------------------------------
 // Two lanes per ray: lane 0 of the pair fetches, filters and shades the even samples, lane 1 the
 // odd ones; both keep the ray position with the same float additions (p_(k+1) = p_k + d step,
@@ -1995,6 +2209,32 @@ __global__ __launch_bounds__(256) void brick_range_kernel(const VT *__restrict__
     if (lane == 0) range[(bz * nby + by) * nbx + bx] = any_nan ? make_float2(NAN, NAN) : make_float2(lo, hi);
 }
 
+// One workgroup: range[nbricks] = {smallest lo, largest hi} over the bricks without a NaN (the
+// MIP kernel ends a ray of an 8/16-bit volume at that maximum).
+__global__ __launch_bounds__(256) void range_max_kernel(float2 *__restrict__ range, uint32_t nbricks)
+{
+    __shared__ float s_lo[4], s_hi[4];
+    float lo = INFINITY, hi = -INFINITY;
+    for (uint32_t b = threadIdx.x; b < nbricks; b += 256) {
+        const float2 r = range[b];
+        lo = fminf(lo, r.x);  // fminf / fmaxf drop a NaN operand
+        hi = fmaxf(hi, r.y);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_xor(lo, off, 64));
+        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        s_lo[threadIdx.x >> 6] = lo;
+        s_hi[threadIdx.x >> 6] = hi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        range[nbricks] = make_float2(fminf(fminf(s_lo[0], s_lo[1]), fminf(s_lo[2], s_lo[3])),
+                                     fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3])));
+}
+
 // One thread per brick: 0 if the brick can produce a visible sample, kSkipCap if EMPTY.
 // Brick b is empty when every density d the trilinear filter can produce from its values maps
 // to TF texels of alpha 0.  d lies in [lo, hi] up to the filter's rounding (3 levels of fmaf
@@ -2297,6 +2537,67 @@ const char *march_kernel_name(int storage, bool shade, bool count, bool skip, bo
     if (storage < 0 || storage > 10) return "march_kernel<?>";
     const int k = (shade ? 16 : 0) + (count ? 8 : 0) + (skip ? 4 : 0) + (gf ? 2 : 0) + (pipe ? 1 : 0);
     return names[storage * 32 + k].c_str();
+}
+
+namespace {
+template <typename VT, bool COUNT, bool SKIP, int K>
+hipError_t launch_mip_t(const MarchParams &p, const MipArgs &m, hipStream_t stream)
+{
+    const uint32_t nblocks = p.tile_perm ? p.nperm
+                             : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
+                                                 : p.tiles_x * p.tiles_y;
+    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
+    hipLaunchKernelGGL((mip_kernel<VT, COUNT, SKIP, K>), dim3(nblocks), dim3(kThreadsPerTile), 0,
+                       stream, p, m);
+    return hipGetLastError();
+}
+template <typename VT>
+hipError_t launch_mip_vt(bool count, int K, const MarchParams &p, const MipArgs &m, hipStream_t s)
+{
+    const bool skip = p.skip_empty != 0;
+    if (skip && !m.brick_range) return hipErrorInvalidValue;
+    if (count)  // the counting kernels walk one step at a time
+        return skip ? launch_mip_t<VT, true, true, 1>(p, m, s) : launch_mip_t<VT, true, false, 1>(p, m, s);
+    switch (K) {
+        case 1: return skip ? launch_mip_t<VT, false, true, 1>(p, m, s) : launch_mip_t<VT, false, false, 1>(p, m, s);
+        case 2: return skip ? launch_mip_t<VT, false, true, 2>(p, m, s) : launch_mip_t<VT, false, false, 2>(p, m, s);
+        case 4: return skip ? launch_mip_t<VT, false, true, 4>(p, m, s) : launch_mip_t<VT, false, false, 4>(p, m, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+}  // namespace
+
+hipError_t launch_mip(int storage, bool count, int K, const MarchParams &p, const MipArgs &m,
+                      hipStream_t stream)
+{
+    switch (storage) {  // the base layouts only: MIP reads no alternative copy
+        case ST_U8: return launch_mip_vt<uint8_t>(count, K, p, m, stream);
+        case ST_I8: return launch_mip_vt<int8_t>(count, K, p, m, stream);
+        case ST_U8 | kQuadFlag: return launch_mip_vt<Quad8<uint8_t>>(count, K, p, m, stream);
+        case ST_I8 | kQuadFlag: return launch_mip_vt<Quad8<int8_t>>(count, K, p, m, stream);
+        case ST_U16: return launch_mip_vt<uint16_t>(count, K, p, m, stream);
+        case ST_I16: return launch_mip_vt<int16_t>(count, K, p, m, stream);
+        case ST_F32: return launch_mip_vt<float>(count, K, p, m, stream);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+std::string mip_kernel_name(int storage, bool count, bool skip, int K)
+{
+    // demangled, as rocprofv3's kernel trace reports it
+    const char *types[7] = {"unsigned char", "signed char", "unsigned short", "short", "float",
+                            "vr::Quad8<unsigned char>", "vr::Quad8<signed char>"};
+    if (storage & kQuadFlag) storage = 5 + (storage & 0xF);
+    if (storage < 0 || storage > 6) return "mip_kernel<?>";
+    return std::string("void vr::(anonymous namespace)::mip_kernel<") + types[storage] +
+           (count ? ", true" : ", false") + (skip ? ", true, " : ", false, ") +
+           std::to_string(count ? 1 : K) + ">(vr::MarchParams, vr::MipArgs)";
+}
+
+hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t s)
+{
+    hipLaunchKernelGGL(range_max_kernel, dim3(1), dim3(256), 0, s, range_dev, nbricks);
+    return hipGetLastError();
 }
 
 hipError_t launch_unbrick(int storage, const void *bricks, void *dst, uint32_t nx, uint32_t ny,

@@ -9,6 +9,7 @@
 //   vr_cli <file.nhdr|file.nrrd|synthetic:N> <out.ppm> [--size WxH] [--radius R]
 //          [--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS]
 //          [--skip-empty] [--frames K] [--device-mask M]   (M: render every frame across these GPUs)
+//          [--mode composite|mip]   (mip: maximum-intensity projection, include/vr/vr_modes.h)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,7 +25,7 @@ int main(int argc, char **argv)
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <file.nhdr|synthetic:N> <out.ppm> [--size WxH] [--radius R] "
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
-                             "[--frames K] [--device-mask M]\n",
+                             "[--frames K] [--device-mask M] [--mode composite|mip]\n",
                      argv[0]);
         return 2;
     }
@@ -33,7 +34,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default";
+    std::string tfname = "default", mode = "composite";
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -44,12 +45,17 @@ int main(int argc, char **argv)
         else if (a == "--exact-gradient") exact_gradient = 1;
         else if (a == "--skip-empty") skip_empty = 1;
         else if (a == "--ert" && i + 1 < argc) ert = std::strtof(argv[++i], nullptr);
+        else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
             std::fprintf(stderr, "unknown argument %s\n", a.c_str());
             return 2;
         }
+    }
+    if (mode != "composite" && mode != "mip") {
+        std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
+        return 2;
     }
     try {
         Vol::Rendering::Hip::OffscreenPass pass = mask ? Vol::Rendering::Hip::OffscreenPass(
@@ -89,6 +95,7 @@ int main(int argc, char **argv)
         Vol::Rendering::Hip::Camera cam{};
         vr_cam_view(&oc, cam.view);
         vr_cam_position(&oc, cam.position);
+        pass.render_mode_changed(mode == "mip" ? VR_MODE_MIP : VR_MODE_COMPOSITE);
         pass.params().shading = shading;
         pass.params().exact_gradient = exact_gradient;
         pass.params().skip_empty = skip_empty;

@@ -121,13 +121,17 @@ DIST_ID_BYTES = 128  # include/vr/vr_dist.h VR_DIST_ID_BYTES
 DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_member",
                  "vr_debug_create_members", "vr_debug_fail_member",
                  "vr_debug_host_profile_enable", "vr_debug_host_profile_member"]
+# include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
+MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
+MODE_COMPOSITE, MODE_MIP = 0, 1
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
 KNOBS = {"pipeline": 1, "pair": 2, "pair_lanes": 3, "grad_field": 4, "u8_layout": 6,
-         "tile_order": 7, "narrow": 8, "alt_geometry": 9}
+         "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10}
 KNOB_AUTO = {"pipeline": -1, "pair": -1, "pair_lanes": 0, "grad_field": -1,
-             "u8_layout": -1, "tile_order": 0, "narrow": 1, "alt_geometry": -1}
+             "u8_layout": -1, "tile_order": 0, "narrow": 1, "alt_geometry": -1,
+             "mip_inflight": 0}
 
 ABI_VERSION = 9  # include/vr/vr.h VR_ABI_VERSION
 _LIB = None
@@ -206,6 +210,8 @@ def lib() -> C.CDLL:
         "vr_memory_report": (i32, [vp, C.POINTER(vr_memory_info)]),
         "vr_prepare": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params)]),
         "vr_debug_get_knob": (i32, [vp, i32, C.POINTER(i32)]),
+        "vr_set_render_mode": (i32, [vp, i32]),
+        "vr_get_render_mode": (i32, [vp, C.POINTER(i32)]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_cam_init": (None, [C.POINTER(vr_orbit_camera)]),
@@ -513,6 +519,16 @@ class OffscreenPass:
         ptr = arr.ctypes.data_as(C.POINTER(C.c_uint32))
         self._check(lib().vr_set_transfer_function(self._ctx, ptr, int(arr.size)),
                     "transfer_function_changed")
+
+    def render_mode_changed(self, mode: int):
+        """vr_set_render_mode (vr_modes.h): MODE_COMPOSITE or MODE_MIP for the frames that follow."""
+        self._check(lib().vr_set_render_mode(self._ctx, int(mode)), "render_mode_changed")
+
+    @property
+    def render_mode(self) -> int:
+        m = C.c_int()
+        self._check(lib().vr_get_render_mode(self._ctx, C.byref(m)), "vr_get_render_mode")
+        return int(m.value)
 
     # -- record/render --
     def render(self, camera: OrbitCamera, params: Optional[vr_params] = None,
