@@ -3,7 +3,7 @@
  *
  * Not part of the drop-in boundary (the reference has no equivalent): the library picks the
  * march kernel variant, the 8-bit brick layout and the tile order from the volume, the view
- * and vr_params alone (DESIGN.md §5 "Which kernel a launch runs").  Every variant renders the
+ * and vr_params alone (DESIGN.md §4.1 "Which kernel a launch runs").  Every variant renders the
  * same bytes, so these knobs change speed, never results -- except VR_KNOB_GRAD_FIELD when
  * vr_params.exact_gradient is 0 (the field then holds binary16 differences, the stencil exact
  * ones); the GPU tests use them to render each variant and compare.  The library never reads the process environment, except in
@@ -98,6 +98,27 @@ int vr_debug_host_profile_member(vr_ctx *ctx, int member, vr_dist_host_profile *
  * VR_EINVAL for an unknown knob or an out-of-range value. */
 int vr_debug_set_knob(vr_ctx *ctx, int knob, int value);
 int vr_debug_get_knob(const vr_ctx *ctx, int knob, int *value);
+
+/* Which kernel a launch runs (csrc/vr_variant.h is the statement of the
+ * table).  vr_variant_facts mirrors the resolved inputs of that decision: `layout` is the
+ * layout code of the copy read (vr_debug_volume_info's storage code, | 0x10 8-bit yz-quads,
+ * | 0x20 / 0x100 / 0x200 the oblique / plain / stencil f32 copy), `mode` a vr_render_mode, the
+ * flags 0 or 1 (skip: granted; field: the difference field is in place, field_half: in
+ * binary16; pipeline: pipelining wanted), pair 0 or the lanes per ray, mip_inflight the MIP
+ * samples in flight.  vr_debug_variant_name is pure (no context, no device): the demangled name
+ * of the kernel such a launch runs, as a profiler reports it, into buf (n bytes, truncated);
+ * VR_EINVAL where no kernel serves the facts (the launch would fail) or on a NULL argument. */
+typedef struct vr_variant_facts {
+    int32_t layout, mode;
+    int32_t shade, count, skip, field, field_half, pipeline;
+    int32_t tf_n, pair, mip_inflight;
+} vr_variant_facts;
+int vr_debug_variant_name(const vr_variant_facts *facts, char *buf, size_t n);
+/* The kernel the context's last frame or vr_count_work launch actually ran -- lane groups, the
+ * granted skip and the copy read included, where vr_kernel_name predicts the single-lane full
+ * frame.  A multi-device context answers for member 0; "" before any launch.  The string is
+ * valid until the calling thread's next call. */
+const char *vr_debug_last_kernel_name(const vr_ctx *ctx);
 
 #ifdef __cplusplus
 }

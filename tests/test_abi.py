@@ -91,9 +91,10 @@ def test_struct_layouts_match_header(tmp_path):
 #include <stdio.h>
 #include <stddef.h>
 #include "vr/vr_debug.h"
-int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(vr_camera), sizeof(vr_params),
+int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(vr_camera), sizeof(vr_params),
   sizeof(vr_stats), offsetof(vr_params, spec_power), offsetof(vr_params, skip_empty), offsetof(vr_params, frames_in_flight), offsetof(vr_params, exact_gradient), offsetof(vr_params, depth_zero_to_one),
-  sizeof(vr_memory_info), sizeof(vr_member_timing), offsetof(vr_member_timing, kernel_ms)); return 0; }
+  sizeof(vr_memory_info), sizeof(vr_member_timing), offsetof(vr_member_timing, kernel_ms),
+  sizeof(vr_variant_facts), offsetof(vr_variant_facts, pipeline), offsetof(vr_variant_facts, mip_inflight)); return 0; }
 """
     tmp = str(tmp_path / "vr_abi_layout")
     with open(tmp + ".c", "w") as f:
@@ -107,7 +108,10 @@ int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", sizeof(
                                      vr_amd.vr_params.exact_gradient.offset,
                                      vr_amd.vr_params.depth_zero_to_one.offset,
                                      C.sizeof(vr_amd.vr_memory_info), C.sizeof(vr_amd.vr_member_timing),
-                                     vr_amd.vr_member_timing.kernel_ms.offset]
+                                     vr_amd.vr_member_timing.kernel_ms.offset,
+                                     C.sizeof(vr_amd.vr_variant_facts),
+                                     vr_amd.vr_variant_facts.pipeline.offset,
+                                     vr_amd.vr_variant_facts.mip_inflight.offset]
     assert "VR_ABI_VERSION 9" in src
 
 

@@ -97,7 +97,7 @@ struct vr_ctx {
         uint32_t tiles_x = 0, tiles_y = 0, supers_x = 0, per_xcd = 0;
         uint32_t row_block = 0, rank = 0, nranks = 0, share_w0 = 1, share_w = 1;
         int pair = 0;
-        uint32_t kernel = 0;  // march variant (tile_kernel_key): its tiles' durations differ
+        uint32_t kernel = 0;  // variant_tile_key: another kernel's tile durations differ
         void *stream = nullptr;
         uint32_t *cost = nullptr, *perm = nullptr, *lists = nullptr;
         bool have_perm = false;
@@ -122,6 +122,7 @@ struct vr_ctx {
     std::vector<Fence> fences;
     uint64_t build_gen = 0;  // records of built_ev so far
     uint64_t frame_no = 0;  // launches so far (the derived structures' recency)
+    FrameVariant last_variant;  // the last frame or count launch (vr_debug_last_kernel_name)
     // derived-structure history (vr_memory_report, ABI 9)
     uint64_t n_builds = 0, n_evictions = 0, n_downgrades = 0;
     uint32_t last_downgrade = 0;
@@ -651,10 +652,10 @@ bool use_pipeline(bool shading, uint32_t tiles, const vr_ctx *c)
 // stay faster single-lane (tools/shard_sweep.py, profiles/r01/multi_gpu/).  Serial frames
 // only (vr_params.frames_in_flight <= 1).  Not for
 // skip-empty frames or TFs beyond the LDS copy.  Knob VR_KNOB_PAIR 0/1 overrides (A/B).
-int want_alt(const vr_ctx *c, const vr_params *p, const MarchParams &P);
+int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field);
 bool use_pair(const vr_ctx *c, const MarchParams &P, const vr_params *p)
 {
-    if (p->skip_empty || P.tf_n > 256) return false;
+    if (p->skip_empty || P.tf_n > kTfLds) return false;
     if (c->knobs.pair >= 0) return c->knobs.pair == 1;
     // frames overlapping on the device: the next frame hides this one's tail, so throughput
     // per sample decides and the single-lane kernel wins (N = 8 C3 share with 3 frames in
@@ -671,7 +672,7 @@ bool use_pair(const vr_ctx *c, const MarchParams &P, const vr_params *p)
     if (c->knobs.alt >= 0 || c->layout != ST_F32 || c->dense_rows || c->pixel_span <= kAltSpan ||
         (c->ray_axis == 2 && c->axis_align >= kAltAlign))
         return false;
-    return want_alt(c, p, P) == (ST_F32 | kAltFlag);
+    return want_alt(c, p, P.pair != 0, P.grad != nullptr) == (ST_F32 | kAltFlag);
 }
 
 int build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
@@ -1163,9 +1164,9 @@ int mip_inflight(const vr_ctx *c, bool skip)
 // bricks on every view whose ray runs along x.  So, off the dense-row views: sparse views along
 // the rows take the plain / stencil copy; axis-aligned views with the ray along y or z and at
 // most kAltSpan voxels per pixel keep the 8^3 bricks; every other view reads the oblique copy.
-int want_alt(const vr_ctx *c, const vr_params *p, const MarchParams &P)
+int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field)
 {
-    if (c->layout != ST_F32 || p->skip_empty || P.pair || P.grad) return c->layout;
+    if (c->layout != ST_F32 || p->skip_empty || pair || field) return c->layout;
     int which = 0;
     if (c->knobs.alt >= 0)
         which = c->knobs.alt;
@@ -1248,14 +1249,45 @@ int ensure_alt(vr_ctx *c, int lay, hipStream_t s, bool *ready)
     return record_build(c, s);
 }
 
-// The march variant a launch runs, as part of the schedule key: a shaded, unshaded or
-// skip-empty frame of the same geometry on the same stream has other tile durations, so one
-// variant's order is not learned from another's (speed only; no measured change on the bench,
-// whose runs use fresh streams).
-uint32_t tile_kernel_key(const MarchParams &P, bool shading, int layout)
+// Which kernel runs (vr_variant.h): the facts of a launch, read from P and `layout` after
+// ensure_mip / ensure_derived, use_pair and want_alt have settled what it reads ...
+VariantFacts launch_facts(const vr_ctx *c, const vr_params *p, const MarchParams &P, int layout,
+                          bool count)
 {
-    return (shading ? 1u : 0u) | (P.skip_empty ? 2u : 0u) | (P.grad ? 4u : 0u) |
-           (P.pipelined ? 8u : 0u) | (P.grad && P.grad_half ? 16u : 0u) | ((uint32_t)layout << 8);
+    const bool mip = c->render_mode == VR_MODE_MIP, skip = P.skip_empty != 0;  // skip: granted
+    return {layout, c->render_mode, p->shading != 0, count, skip, P.grad != nullptr, P.grad_half,
+            P.pipelined, P.tf_n, P.pair, mip ? mip_inflight(c, skip) : 0};
+}
+// ... and the facts vr_kernel_name predicts from the context for the next full frame (vr.h:
+// row_block 16, one rank, a single lane per ray, the last view).  It cannot build anything,
+// so it differs from launch_facts where the launch would:
+//   skip   composite: as requested (the launch: as granted -- the memory budget may refuse the
+//          skip structures); MIP: only once the brick ranges are in place;
+//   field  only once a shaded frame has built it (the launch builds it when the policy wants it);
+//   layout an alternative copy only once it exists (the launch builds it);
+//   pair   never (documented: the single-lane variant, also where the frame runs lane groups).
+VariantFacts next_frame_facts(const vr_ctx *c, const vr_params *p)
+{
+    VariantFacts f{};
+    f.layout = c->layout;
+    f.mode = c->render_mode;
+    f.shade = p && p->shading;
+    f.tf_n = (int32_t)c->tf_n;
+    if (f.mode == VR_MODE_MIP) {
+        f.skip = p && p->skip_empty && c->range_valid && c->nbricks_alloc;
+        f.mip_inflight = mip_inflight(c, f.skip);
+        return f;
+    }
+    f.skip = p && p->skip_empty;
+    f.field = f.shade && use_grad_field(c, p->exact_gradient == 0) && c->grad && c->grad_valid;
+    f.field_half = f.field && p->exact_gradient == 0;
+    const uint32_t tiles = ((c->width + 15) / 16) * ((c->height + kMarchRows - 1) / kMarchRows);
+    f.pipeline = use_pipeline(f.shade, tiles, c);
+    if (p && !f.field)
+        if (const int lay = want_alt(c, p, false, false);
+            lay != c->layout && c->alt[alt_index(lay)].valid)
+            f.layout = lay;
+    return f;
 }
 
 // Adaptive tile order (tile_order 4): the schedule entry of this launch geometry (created on
@@ -2169,62 +2201,37 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
     hipStream_t s = static_cast<hipStream_t>(stream);
     ++c->frame_no;
     uint32_t refused = 0;  // VR_DERIVED_* the budget or free memory refused this frame
-    if (c->render_mode == VR_MODE_MIP) {
-        MipArgs M;
+    MipArgs M{nullptr, 0};
+    int layout = c->layout;
+    const bool mip = c->render_mode == VR_MODE_MIP;
+    if (mip) {  // the base bricks and, with skip_empty, the brick ranges
         rc = ensure_mip(c, p, P, M, s, &refused);
         if (rc) return rc;
-        if (!launch) return VR_OK;
-        if (refused) {
-            ++c->n_downgrades;
-            c->last_downgrade = refused;
-        }
-        const int K = mip_inflight(c, P.skip_empty != 0);
-        vr_ctx::TileSched *ts = tile_sched(c, P, stream, 0x40000000u | (P.skip_empty ? 2u : 0u) |
-                                                            ((uint32_t)K << 2) | ((uint32_t)c->layout << 8));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        const bool timing = c->timing;
-        if (timing) {
-            e0 = pooled_event(c);
-            e1 = pooled_event(c);
-            if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-            HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-        }
-        HIP_TRY(c, launch_mip(c->layout, false, K, P, M, s), "mip kernel launch");
-        if (timing) {
-            HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-            c->ev_pending.emplace_back(e0, e1);
-        }
-        if (ts && ts->launches++ % kReorderEvery == 0) {
-            HIP_TRY(c, launch_order_tiles(ts->cost, ts->lists, ts->perm, ts->per_xcd, s),
-                    "tile order kernel");
-            ts->have_perm = true;
-        }
-        return fence_record(c, s);
-    }
-    rc = ensure_derived(c, p, P, s, &refused);
-    if (rc) return rc;
-    if (use_pair(c, P, p)) {  // L lanes per ray on 16 x (16 / L) tiles (march_pair_kernel)
-        // 4 lanes below kPairQuadMaxWaves (N = 8 C3 share: 0.151 -> 0.144 ms), else 2
-        P.pair = P.tiles_x * P.tiles_y * (kThreadsPerTile / 64) < kPairQuadMaxWaves ? 4 : 2;
-        if (c->knobs.pair_lanes == 2 || c->knobs.pair_lanes == 4) P.pair = c->knobs.pair_lanes;
-        const uint32_t th = 16 / P.pair;
-        P.tiles_y = (P.local_rows + th - 1) / th;
-        P.supers_total = P.supers_x * ((P.tiles_y + kSuper - 1) / kSuper);
-    }
-    // oblique and sparse f32 views: an alternative-geometry copy (want_alt)
-    int layout = c->layout;
-    if (const int lay = want_alt(c, p, P); lay != c->layout) {
-        bool ready = false;
-        rc = ensure_alt(c, lay, s, &ready);
+    } else {
+        rc = ensure_derived(c, p, P, s, &refused);
         if (rc) return rc;
-        if (ready) {
-            layout = lay;
-            P.vol = c->alt[alt_index(lay)].bricks;
-            P.vol_bytes = c->alt[alt_index(lay)].bytes;
-            P.nbx = bricks_for(c->nx, 0, layout);
-            P.nby = bricks_for(c->ny, 1, layout);
-        } else {
-            refused = (uint32_t)(VR_DERIVED_OBLIQUE_COPY + alt_index(lay));
+        if (use_pair(c, P, p)) {  // L lanes per ray on 16 x (16 / L) tiles (march_pair_kernel)
+            // 4 lanes below kPairQuadMaxWaves (N = 8 C3 share: 0.151 -> 0.144 ms), else 2
+            P.pair = P.tiles_x * P.tiles_y * (kThreadsPerTile / 64) < kPairQuadMaxWaves ? 4 : 2;
+            if (c->knobs.pair_lanes == 2 || c->knobs.pair_lanes == 4) P.pair = c->knobs.pair_lanes;
+            const uint32_t th = 16 / P.pair;
+            P.tiles_y = (P.local_rows + th - 1) / th;
+            P.supers_total = P.supers_x * ((P.tiles_y + kSuper - 1) / kSuper);
+        }
+        // oblique and sparse f32 views: an alternative-geometry copy (want_alt)
+        if (const int lay = want_alt(c, p, P.pair != 0, P.grad != nullptr); lay != c->layout) {
+            bool ready = false;
+            rc = ensure_alt(c, lay, s, &ready);
+            if (rc) return rc;
+            if (ready) {
+                layout = lay;
+                P.vol = c->alt[alt_index(lay)].bricks;
+                P.vol_bytes = c->alt[alt_index(lay)].bytes;
+                P.nbx = bricks_for(c->nx, 0, layout);
+                P.nby = bricks_for(c->ny, 1, layout);
+            } else {
+                refused = (uint32_t)(VR_DERIVED_OBLIQUE_COPY + alt_index(lay));
+            }
         }
     }
     if (!launch) return VR_OK;
@@ -2232,8 +2239,9 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
         ++c->n_downgrades;
         c->last_downgrade = refused;
     }
-    vr_ctx::TileSched *ts =
-        tile_sched(c, P, stream, tile_kernel_key(P, p->shading != 0, layout));
+    FrameVariant v;  // VF_NONE where no kernel serves the facts: launch_frame then fails
+    resolve_variant(launch_facts(c, p, P, layout, false), &v);
+    vr_ctx::TileSched *ts = tile_sched(c, P, stream, variant_tile_key(v, layout));
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const bool timing = c->timing;  // read once: the pair is recorded and queued together
     if (timing) {
@@ -2242,13 +2250,14 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
         if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
         HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
     }
-    HIP_TRY(c, launch_march(layout, p->shading != 0, false, P, s), "march kernel launch");
+    HIP_TRY(c, launch_frame(v, P, M, s), mip ? "mip kernel launch" : "march kernel launch");
+    c->last_variant = v;
     if (timing) {
         HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
         c->ev_pending.emplace_back(e0, e1);
     }
     // next launches of this geometry: longest tiles first, re-ordered every kReorderEvery
-    // launches (the order kernel runs after the timed march kernel, inside the frame)
+    // launches (the order kernel runs after the timed frame kernel, inside the frame)
     if (ts && ts->launches++ % kReorderEvery == 0) {
         HIP_TRY(c, launch_order_tiles(ts->cost, ts->lists, ts->perm, ts->per_xcd, s),
                 "tile order kernel");
@@ -2445,15 +2454,15 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
                           c->share, P);
     if (rc) return rc;
     uint32_t refused = 0;  // a count is not a frame: not a downgrade
-    MipArgs M;
+    MipArgs M{nullptr, 0};
     const bool mip = c->render_mode == VR_MODE_MIP;
     rc = mip ? ensure_mip(c, p, P, M, nullptr, &refused) : ensure_derived(c, p, P, nullptr, &refused);
     if (rc) return rc;
     HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
-    if (mip)
-        HIP_TRY(c, launch_mip(c->layout, true, 1, P, M, nullptr), "mip (count) launch");
-    else
-        HIP_TRY(c, launch_march(c->layout, p->shading != 0, true, P, nullptr), "march (count) launch");
+    FrameVariant v;
+    resolve_variant(launch_facts(c, p, P, c->layout, true), &v);
+    HIP_TRY(c, launch_frame(v, P, M, nullptr), mip ? "mip (count) launch" : "march (count) launch");
+    c->last_variant = v;
     unsigned long long h[5];
     HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
     out->rays = h[0];
@@ -2590,29 +2599,28 @@ const char *vr_kernel_name(const vr_ctx *c, const vr_params *p)
 {
     if (!c) return "";
     if (is_group(c)) return vr_kernel_name(c->members[0], p);
-    if (c->render_mode == VR_MODE_MIP) {  // range skipping once the ranges are in place
-        thread_local std::string name;
-        const bool skip = p && p->skip_empty && c->range_valid && c->nbricks_alloc;
-        name = mip_kernel_name(c->layout, false, skip, mip_inflight(c, skip));  // of the last view
-        return name.c_str();
-    }
-    // the variant the next vr_render_device launches (after a shaded frame built the field)
-    const bool gf = p && p->shading && use_grad_field(c, p->exact_gradient == 0) && c->grad &&
-                    c->grad_valid;
-    // the full frame (row_block 16, one rank), as vr_render launches it
-    const uint32_t tiles = ((c->width + 15) / 16) * ((c->height + kMarchRows - 1) / kMarchRows);
-    const bool pipe = use_pipeline(p && p->shading, tiles, c) &&
-                      !(p && p->skip_empty) && c->tf_n <= 256;
-    int layout = c->layout;
-    if (p && !gf) {  // want_alt for the full frame of the last view, once its copy exists
-        MarchParams P;
-        std::memset(&P, 0, sizeof P);
-        const int lay = want_alt(c, p, P);
-        if (lay != c->layout && c->alt[alt_index(lay)].valid) layout = lay;
-    }
-    if (gf && p->exact_gradient == 0 && c->storage == ST_F32) layout |= kHalfFieldFlag;
-    return march_kernel_name(layout, p && p->shading != 0, false, p && p->skip_empty != 0, gf,
-                             pipe);
+    thread_local std::string name;
+    FrameVariant v;
+    resolve_variant(next_frame_facts(c, p), &v);
+    name = variant_kernel_name(v);
+    return name.c_str();
+}
+
+int vr_debug_variant_name(const vr_variant_facts *facts, char *buf, size_t n)
+{
+    FrameVariant v;
+    if (!facts || !buf || n == 0 || !resolve_variant(*facts, &v)) return VR_EINVAL;
+    std::snprintf(buf, n, "%s", variant_kernel_name(v).c_str());
+    return VR_OK;
+}
+
+const char *vr_debug_last_kernel_name(const vr_ctx *c)
+{
+    if (!c) return "";
+    if (is_group(c)) return vr_debug_last_kernel_name(c->members[0]);
+    thread_local std::string name;
+    name = variant_kernel_name(c->last_variant);
+    return name.c_str();
 }
 
 int vr_debug_set_knob(vr_ctx *c, int knob, int value)

@@ -7,8 +7,9 @@
 #include <stdint.h>
 
 #include <cmath>
-#include <string>
 #include <type_traits>
+
+#include "vr_variant.h"
 
 namespace vr {
 
@@ -134,13 +135,12 @@ __host__ __device__ __forceinline__ void brick_coords(uint32_t slot, uint32_t nb
     }
 }
 
-enum StorageType { ST_U8 = 0, ST_I8 = 1, ST_U16 = 2, ST_I16 = 3, ST_F32 = 4 };
+// (enum StorageType and the layout flags named below: vr_variant.h)
 // Brick layout code = storage type | kQuadFlag: 8-bit voxels kept in yz-quad elements (GeomWide
 // bricks, one 8-B load per sample) instead of plain 7x8x8-cell bricks.  Volumes of at most
 // kQuadMaxVoxels voxels use it (the quads, 5.7x the voxels, stay cache-resident: C2 256^3
 // 459 against 420 Gsamples/s plain); larger ones the plain bricks (C4 HBM 5.70 -> 1.89 GB per
 // frame).  The layout code is what the brick helpers below and the march launchers take.
-constexpr int kQuadFlag = 0x10;
 constexpr size_t kQuadMaxVoxels = 1ull << 25;
 // kernel-side tag type of 8-bit voxels T in yz-quad elements
 template <typename T>
@@ -155,7 +155,6 @@ struct Quad8 {
 // The frame-filling, side and top views stay in 8^3 bricks (2-4% faster there).  (A 15 x 15 x 8
 // z-pair copy for sparse views, superseded by the plain and stencil copies below, is kept as a
 // patch: tools/experiments/r04_pruned/.)
-constexpr int kAltFlag = 0x20;
 #ifndef VR_ALT_BRICK_CELLS
 #define VR_ALT_BRICK_CELLS 7, 15, 8
 #endif
@@ -168,7 +167,6 @@ struct F32Alt {
 // duplication (1.2x the voxels against 2.6x), in GeomPlainRows bricks; a sample is 4 x 8-B
 // loads (elements x, x + 1 of the rows (y | y+1, z | z+1)).  For sparse views, which read their
 // whole copy from HBM every frame.
-constexpr int kPlainF32Flag = 0x100;
 #ifndef VR_PLAIN_BRICK_CELLS
 #define VR_PLAIN_BRICK_CELLS 15, 15, 15
 #endif
@@ -184,7 +182,6 @@ struct F32P {
 // loads, no neighbour-brick selection.  For shaded sparse views: the
 // reference's default camera 0.260 (15x15x8 z-pairs) -> 0.231 ms (profiles/r03/stencil2/ ..
 // stencil4/: 13^3 cells 0.240, 29x13x13 0.236, 29x13x29 / 29x13x61 / 29^3 0.231).
-constexpr int kStencilF32Flag = 0x200;
 #ifndef VR_STENCIL_BRICK_CELLS
 #define VR_STENCIL_BRICK_CELLS 29, 29, 29
 #endif
@@ -193,12 +190,10 @@ struct F32S {
     float v;
 };
 // kernel-side tag type of the f32 8^3-brick volume read with the difference field in binary16
-// (MarchParams::grad_half); kHalfFieldFlag marks that variant in kernel names and schedule keys
-// only (the bricks are the ST_F32 ones)
+// (MarchParams::grad_half): a variant of its own (vr_variant.h TAG_F32H) over the ST_F32 bricks
 struct F32H {
     float v;
 };
-constexpr int kHalfFieldFlag = 0x80;
 
 // Bytes of one voxel of storage type (or layout code) st.
 inline size_t storage_size(int st)
@@ -363,9 +358,6 @@ struct MarchParams {
 };
 
 // Launchers (vr_kernels.hip).  All asynchronous on `stream`.
-hipError_t launch_march(int storage, bool shade, bool count, const MarchParams &p,
-                        hipStream_t stream);
-const char *march_kernel_name(int storage, bool shade, bool count, bool skip, bool gf, bool pipe);
 // ---- Maximum-intensity projection (include/vr/vr_modes.h, mip_kernel) ----
 // What the MIP kernel reads beside MarchParams (a kernel argument of its own: MarchParams'
 // size is part of the composite kernels' descriptors, which the committed roofline data is
@@ -376,11 +368,10 @@ struct MipArgs {
     const float2 *brick_range;
     uint32_t nbricks;
 };
-// K: samples of a ray in flight (1, 2 or 4).  The layout is a base one (no alternative f32
-// copy); skip follows p.skip_empty (then m.brick_range is set).
-hipError_t launch_mip(int storage, bool count, int K, const MarchParams &p, const MipArgs &m,
-                      hipStream_t stream);
-std::string mip_kernel_name(int storage, bool count, bool skip, int K);
+// The kernel `v` names (resolve_variant) over p's tiles; m is read by mip_kernel alone.
+// hipErrorInvalidValue: no such kernel (variant_built), or MIP skipping without m.brick_range.
+hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
+                        hipStream_t stream);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

@@ -26,10 +26,11 @@
 #include "vr_exact_math.h"
 #include "vr_internal.h"
 
+#include <array>
 #include <cstdlib>
-#include <string>
+#include <tuple>
 #include <type_traits>
-#include <vector>
+#include <utility>
 
 #pragma clang fp contract(off)
 
@@ -38,7 +39,6 @@ namespace {
 
 constexpr int kTile = 16;       // pixels per workgroup side
 constexpr int kThreads = 256;   // lane-pair kernel workgroup: 4 waves
-constexpr int kTfLds = 256;     // TF texels staged in LDS
 constexpr int kTfLut = 2 * (kTfLds + 2);  // float4s of the staged LUT (tf_lookup: + 2 sentinels)
 
 __device__ __forceinline__ float lerpf(float a, float b, float w) { return fmaf(w, b - a, a); }
@@ -2336,98 +2336,42 @@ static uint32_t march_lds_pad()
 constexpr uint32_t march_lds_pad() { return 0; }
 #endif
 
-template <typename VT, bool SHADE, bool COUNT, bool SKIP, bool GF = false, bool PIPE = false>
-hipError_t launch_march_t(const MarchParams &p, hipStream_t stream)
-{
-    const uint32_t nblocks = p.tile_perm ? p.nperm
-                             : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
-                                                 : p.tiles_x * p.tiles_y;
-    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
-    hipLaunchKernelGGL((march_kernel<VT, SHADE, COUNT, SKIP, GF, PIPE>), dim3(nblocks), dim3(kThreadsPerTile),
-                       march_lds_pad(), stream, p);
-    return hipGetLastError();
-}
+// launch_frame: the kernels' storage type tags in VariantTag order (vr_variant.h), and one
+// launcher per variant slot -- null where the library carries no such kernel (variant_built),
+// so exactly the instantiations listed there exist.
+using VariantTypes = std::tuple<uint8_t, int8_t, uint16_t, int16_t, float, Quad8<uint8_t>,
+                                Quad8<int8_t>, F32Alt, F32H, F32P, F32S>;
+static_assert(std::tuple_size<VariantTypes>::value == kVariantTags, "one type per VariantTag");
+using FrameLauncher = void (*)(uint32_t nblocks, const MarchParams &, const MipArgs &, hipStream_t);
 
-template <typename VT, bool SHADE, bool GF>
-hipError_t launch_pair_t(const MarchParams &p, hipStream_t stream)
+template <int I>
+void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, hipStream_t stream)
 {
-    const uint32_t nblocks = p.tile_perm ? p.nperm
-                             : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
-                                                 : p.tiles_x * p.tiles_y;
-    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
-    if (p.pair == 4)
-        hipLaunchKernelGGL((march_pair_kernel<VT, SHADE, GF, 4>), dim3(nblocks), dim3(kThreads),
-                           0, stream, p);
+    constexpr FrameVariant v = variant_at(I);
+    using VT = std::tuple_element_t<v.tag, VariantTypes>;
+    if constexpr (v.family == VF_MARCH)
+        hipLaunchKernelGGL((march_kernel<VT, v.shade, v.count, v.skip, v.gf, v.pipe>), dim3(nblocks),
+                           dim3(kThreadsPerTile), march_lds_pad(), stream, p);
+    else if constexpr (v.family == VF_PAIR)
+        hipLaunchKernelGGL((march_pair_kernel<VT, v.shade, v.gf, v.lanes>), dim3(nblocks),
+                           dim3(kThreads), 0, stream, p);
     else
-        hipLaunchKernelGGL((march_pair_kernel<VT, SHADE, GF, 2>), dim3(nblocks), dim3(kThreads),
-                           0, stream, p);
-    return hipGetLastError();
+        hipLaunchKernelGGL((mip_kernel<VT, v.count, v.skip, v.inflight>), dim3(nblocks),
+                           dim3(kThreadsPerTile), 0, stream, p, m);
 }
 
-template <typename VT>
-hipError_t launch_march_vt(bool shade, bool count, const MarchParams &p, hipStream_t s)
+template <int I>
+constexpr FrameLauncher slot_launcher()
 {
-    if (p.pair) {  // host: not counting, no skip-empty, tf_n <= kTfLds, 16x8 tiles
-        if (!shade) return launch_pair_t<VT, false, false>(p, s);
-        if constexpr (kZPair<VT>)
-            if (p.grad) return launch_pair_t<VT, true, true>(p, s);
-        return launch_pair_t<VT, true, false>(p, s);
-    }
-    if (p.pipelined && !count && !p.skip_empty && p.tf_n <= kTfLds) {
-        if (!shade) return launch_march_t<VT, false, false, false, false, true>(p, s);
-        if constexpr (kZPair<VT>)
-            if (p.grad) return launch_march_t<VT, true, false, false, true, true>(p, s);
-        return launch_march_t<VT, true, false, false, false, true>(p, s);
-    }
-    if constexpr (kZPair<VT>) {
-        if (shade && p.grad) {
-            if (p.skip_empty)
-                return count ? launch_march_t<VT, true, true, true, true>(p, s)
-                             : launch_march_t<VT, true, false, true, true>(p, s);
-            return count ? launch_march_t<VT, true, true, false, true>(p, s)
-                         : launch_march_t<VT, true, false, false, true>(p, s);
-        }
-    }
-    if (p.skip_empty) {
-        if (shade)
-            return count ? launch_march_t<VT, true, true, true>(p, s)
-                         : launch_march_t<VT, true, false, true>(p, s);
-        return count ? launch_march_t<VT, false, true, true>(p, s)
-                     : launch_march_t<VT, false, false, true>(p, s);
-    }
-    if (shade)
-        return count ? launch_march_t<VT, true, true, false>(p, s)
-                     : launch_march_t<VT, true, false, false>(p, s);
-    return count ? launch_march_t<VT, false, true, false>(p, s)
-                 : launch_march_t<VT, false, false, false>(p, s);
+    if constexpr (variant_built(variant_at(I)) && variant_index(variant_at(I)) == I)
+        return &launch_slot<I>;
+    else
+        return nullptr;
 }
-
-// The f32 volume with the binary16 difference field (MarchParams::grad_half; shaded launches
-// that read the field, not LDS-staged): the field variants of launch_march_vt.
-template <typename VT>
-hipError_t launch_march_half_field(bool count, const MarchParams &p, hipStream_t s)
+template <int... I>
+constexpr std::array<FrameLauncher, sizeof...(I)> slot_launchers(std::integer_sequence<int, I...>)
 {
-    if (p.pair) return launch_pair_t<VT, true, true>(p, s);
-    if (p.pipelined && !count && !p.skip_empty && p.tf_n <= kTfLds)
-        return launch_march_t<VT, true, false, false, true, true>(p, s);
-    if (p.skip_empty)
-        return count ? launch_march_t<VT, true, true, true, true>(p, s)
-                     : launch_march_t<VT, true, false, true, true>(p, s);
-    return count ? launch_march_t<VT, true, true, false, true>(p, s)
-                 : launch_march_t<VT, true, false, false, true>(p, s);
-}
-
-// The f32 volume's GeomAlt copy (kAltFlag) serves full-frame launches without skip-empty, the
-// difference field, lane groups or LDS staging (the host picks it for oblique and sparse views
-// only): single-stage or pipelined, shaded (stencil gradient) or not.
-template <typename VT>
-hipError_t launch_march_alt(bool shade, const MarchParams &p, hipStream_t s)
-{
-    if (p.pipelined && p.tf_n <= kTfLds)
-        return shade ? launch_march_t<VT, true, false, false, false, true>(p, s)
-                     : launch_march_t<VT, false, false, false, false, true>(p, s);
-    return shade ? launch_march_t<VT, true, false, false>(p, s)
-                 : launch_march_t<VT, false, false, false>(p, s);
+    return {{slot_launcher<I>()...}};
 }
 
 // workgroups for the per-brick kernels (brick_kernel, grad_field_kernel): one per brick
@@ -2487,111 +2431,19 @@ hipError_t brick_from(const void *src, void *dst, uint32_t nx, uint32_t ny, uint
 
 }  // namespace
 
-hipError_t launch_march(int storage, bool shade, bool count, const MarchParams &p,
+hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
                         hipStream_t stream)
 {
-    switch (storage) {
-        case ST_U8: return launch_march_vt<uint8_t>(shade, count, p, stream);
-        case ST_I8: return launch_march_vt<int8_t>(shade, count, p, stream);
-        case ST_U8 | kQuadFlag: return launch_march_vt<Quad8<uint8_t>>(shade, count, p, stream);
-        case ST_I8 | kQuadFlag: return launch_march_vt<Quad8<int8_t>>(shade, count, p, stream);
-        case ST_U16: return launch_march_vt<uint16_t>(shade, count, p, stream);
-        case ST_I16: return launch_march_vt<int16_t>(shade, count, p, stream);
-        case ST_F32:
-            if (shade && p.grad && p.grad_half)
-                return launch_march_half_field<F32H>(count, p, stream);
-            return launch_march_vt<float>(shade, count, p, stream);
-        case ST_F32 | kAltFlag:
-        case ST_F32 | kPlainF32Flag:
-        case ST_F32 | kStencilF32Flag:
-            if (count || p.pair || p.skip_empty || p.grad) return hipErrorInvalidValue;
-            if (storage & kPlainF32Flag) return launch_march_alt<F32P>(shade, p, stream);
-            if (storage & kStencilF32Flag) return launch_march_alt<F32S>(shade, p, stream);
-            return launch_march_alt<F32Alt>(shade, p, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-const char *march_kernel_name(int storage, bool shade, bool count, bool skip, bool gf, bool pipe)
-{
-    // demangled names as rocprofv3 reports them (kernel-trace "Kernel_Name"); storage is the
-    // layout code (8-bit yz-quads: the Quad8 instantiations)
-    static const std::vector<std::string> names = [] {
-        const char *types[11] = {"unsigned char", "signed char", "unsigned short", "short", "float",
-                                 "vr::Quad8<unsigned char>", "vr::Quad8<signed char>", "vr::F32Alt",
-                                 "vr::F32H", "vr::F32P", "vr::F32S"};
-        std::vector<std::string> v;
-        for (int t = 0; t < 11; ++t)
-            for (int k = 0; k < 32; ++k) {
-                std::string n = std::string("void vr::(anonymous namespace)::march_kernel<") + types[t];
-                for (int bit = 4; bit >= 0; --bit) n += (k >> bit) & 1 ? ", true" : ", false";
-                v.push_back(n + ">(vr::MarchParams)");
-            }
-        return v;
-    }();
-    if (storage & kQuadFlag) storage = 5 + (storage & 0xF);
-    if (storage & kAltFlag) storage = 7;
-    if (storage & kHalfFieldFlag) storage = 8;
-    if (storage & kPlainF32Flag) storage = 9;
-    if (storage & kStencilF32Flag) storage = 10;
-    if (storage < 0 || storage > 10) return "march_kernel<?>";
-    const int k = (shade ? 16 : 0) + (count ? 8 : 0) + (skip ? 4 : 0) + (gf ? 2 : 0) + (pipe ? 1 : 0);
-    return names[storage * 32 + k].c_str();
-}
-
-namespace {
-template <typename VT, bool COUNT, bool SKIP, int K>
-hipError_t launch_mip_t(const MarchParams &p, const MipArgs &m, hipStream_t stream)
-{
+    static constexpr auto launchers = slot_launchers(std::make_integer_sequence<int, kVariantSlots>{});
+    const int i = variant_index(v);
+    const FrameLauncher fn = i >= 0 && i < kVariantSlots ? launchers[(size_t)i] : nullptr;
+    if (!fn || (v.family == VF_MIP && v.skip && !m.brick_range)) return hipErrorInvalidValue;
+    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
     const uint32_t nblocks = p.tile_perm ? p.nperm
                              : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
                                                  : p.tiles_x * p.tiles_y;
-    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
-    hipLaunchKernelGGL((mip_kernel<VT, COUNT, SKIP, K>), dim3(nblocks), dim3(kThreadsPerTile), 0,
-                       stream, p, m);
+    fn(nblocks, p, m, stream);
     return hipGetLastError();
-}
-template <typename VT>
-hipError_t launch_mip_vt(bool count, int K, const MarchParams &p, const MipArgs &m, hipStream_t s)
-{
-    const bool skip = p.skip_empty != 0;
-    if (skip && !m.brick_range) return hipErrorInvalidValue;
-    if (count)  // the counting kernels walk one step at a time
-        return skip ? launch_mip_t<VT, true, true, 1>(p, m, s) : launch_mip_t<VT, true, false, 1>(p, m, s);
-    switch (K) {
-        case 1: return skip ? launch_mip_t<VT, false, true, 1>(p, m, s) : launch_mip_t<VT, false, false, 1>(p, m, s);
-        case 2: return skip ? launch_mip_t<VT, false, true, 2>(p, m, s) : launch_mip_t<VT, false, false, 2>(p, m, s);
-        case 4: return skip ? launch_mip_t<VT, false, true, 4>(p, m, s) : launch_mip_t<VT, false, false, 4>(p, m, s);
-        default: return hipErrorInvalidValue;
-    }
-}
-}  // namespace
-
-hipError_t launch_mip(int storage, bool count, int K, const MarchParams &p, const MipArgs &m,
-                      hipStream_t stream)
-{
-    switch (storage) {  // the base layouts only: MIP reads no alternative copy
-        case ST_U8: return launch_mip_vt<uint8_t>(count, K, p, m, stream);
-        case ST_I8: return launch_mip_vt<int8_t>(count, K, p, m, stream);
-        case ST_U8 | kQuadFlag: return launch_mip_vt<Quad8<uint8_t>>(count, K, p, m, stream);
-        case ST_I8 | kQuadFlag: return launch_mip_vt<Quad8<int8_t>>(count, K, p, m, stream);
-        case ST_U16: return launch_mip_vt<uint16_t>(count, K, p, m, stream);
-        case ST_I16: return launch_mip_vt<int16_t>(count, K, p, m, stream);
-        case ST_F32: return launch_mip_vt<float>(count, K, p, m, stream);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-std::string mip_kernel_name(int storage, bool count, bool skip, int K)
-{
-    // demangled, as rocprofv3's kernel trace reports it
-    const char *types[7] = {"unsigned char", "signed char", "unsigned short", "short", "float",
-                            "vr::Quad8<unsigned char>", "vr::Quad8<signed char>"};
-    if (storage & kQuadFlag) storage = 5 + (storage & 0xF);
-    if (storage < 0 || storage > 6) return "mip_kernel<?>";
-    return std::string("void vr::(anonymous namespace)::mip_kernel<") + types[storage] +
-           (count ? ", true" : ", false") + (skip ? ", true, " : ", false, ") +
-           std::to_string(count ? 1 : K) + ">(vr::MarchParams, vr::MipArgs)";
 }
 
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t s)

@@ -84,6 +84,12 @@ class vr_member_timing(C.Structure):  # vr_debug.h (ABI 7)
                 ("render_ms", C.c_double), ("gather_ms", C.c_double), ("assemble_ms", C.c_double)]
 
 
+class vr_variant_facts(C.Structure):  # vr_debug.h
+    _fields_ = [(n, C.c_int32) for n in (
+        "layout", "mode", "shade", "count", "skip", "field", "field_half", "pipeline", "tf_n",
+        "pair", "mip_inflight")]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -120,7 +126,8 @@ DIST_SYMBOLS = [
 DIST_ID_BYTES = 128  # include/vr/vr_dist.h VR_DIST_ID_BYTES
 DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_member",
                  "vr_debug_create_members", "vr_debug_fail_member",
-                 "vr_debug_host_profile_enable", "vr_debug_host_profile_member"]
+                 "vr_debug_host_profile_enable", "vr_debug_host_profile_member",
+                 "vr_debug_variant_name", "vr_debug_last_kernel_name"]
 # include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
 MODE_COMPOSITE, MODE_MIP = 0, 1
@@ -214,6 +221,8 @@ def lib() -> C.CDLL:
         "vr_get_render_mode": (i32, [vp, C.POINTER(i32)]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
+        "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
+        "vr_debug_last_kernel_name": (C.c_char_p, [vp]),
         "vr_cam_init": (None, [C.POINTER(vr_orbit_camera)]),
         "vr_cam_rotate": (None, [C.POINTER(vr_orbit_camera), f32, f32]),
         "vr_cam_zoom": (None, [C.POINTER(vr_orbit_camera), f32]),
@@ -582,6 +591,10 @@ class OffscreenPass:
     def kernel_name(self, params) -> str:
         return lib().vr_kernel_name(self._ctx, C.byref(params)).decode()
 
+    def last_kernel_name(self) -> str:
+        """vr_debug_last_kernel_name: the kernel the last frame or count launch actually ran."""
+        return lib().vr_debug_last_kernel_name(self._ctx).decode()
+
     def timing_member(self, member: int) -> dict:
         """vr_debug_timing_member: one device's summed kernel / render / gather / assembly ms."""
         t = vr_member_timing()
@@ -750,17 +763,10 @@ def _elf_sections(b: bytes, base: int = 0):
     return [(b[names + s[0]:b.index(b"\0", names + s[0])],) + s for s in secs]
 
 
-def kernel_code_hash(path: Optional[str] = None) -> str:
-    """sha256 (16 hex digits) of the frame kernels' machine code in the library: every
-    instantiation of march_kernel, march_pair_kernel (lane groups: small row shares) and
-    order_tiles_kernel (the adaptive tile order inside a frame) -- gfx950 code bytes and kernel
-    descriptor (register counts, LDS, kernarg size; the descriptor's layout-dependent
-    code-entry offset zeroed), read from the code object in the `.hip_fatbin` ELF section.
-    Keys measured per-kernel figures (the PMC traffic bench.py's roofline reads) to the machine
-    code they were measured on: host-only edits and changes to other kernels leave it
-    unchanged, any change to a kernel a frame launches moves it (the build is deterministic;
-    ADVICE r5: the pair and tile-order kernels were not hashed before)."""
-    import hashlib
+def code_object_symbols(path: Optional[str] = None):
+    """(name, bytes) of every sized symbol of the library's gfx950 code object (the
+    `.hip_fatbin` ELF section): kernels' code bytes, and under `<kernel>.kd` their descriptors
+    (register counts, LDS, kernarg size) with the layout-dependent code-entry offset zeroed."""
     import re
     import struct
     b = open(path or LIB_PATH, "rb").read()
@@ -768,7 +774,6 @@ def kernel_code_hash(path: Optional[str] = None) -> str:
     if not fb:
         raise RuntimeError(f"{path or LIB_PATH} has no .hip_fatbin section")
     fat = b[fb[0][5]:fb[0][5] + fb[0][6]]
-    syms = []
     for p in (m.start() for m in re.finditer(b"__CLANG_OFFLOAD_BUNDLE__", fat)):
         q = p + 32
         for _ in range(struct.unpack_from("<Q", fat, p + 24)[0]):
@@ -784,14 +789,27 @@ def kernel_code_hash(path: Optional[str] = None) -> str:
             for i in range(st[6] // 24):
                 nm, _, _, shndx, val, sz = struct.unpack_from("<IBBHQQ", co, st[5] + i * 24)
                 name = co[strt[5] + nm:co.index(b"\0", strt[5] + nm)]
-                frame_kernel = any(k in name for k in (b"12march_kernel", b"17march_pair_kernel",
-                                                         b"18order_tiles_kernel"))
-                if frame_kernel and 0 < shndx < len(secs) and sz > 0:
+                if 0 < shndx < len(secs) and sz > 0:
                     sec = secs[shndx]
                     code = bytearray(co[sec[5] + val - sec[4]:sec[5] + val - sec[4] + sz])
                     if name.endswith(b".kd") and len(code) >= 24:
                         code[16:24] = bytes(8)  # kernel_code_entry_byte_offset
-                    syms.append((name, bytes(code)))
+                    yield name, bytes(code)
+
+
+def kernel_code_hash(path: Optional[str] = None) -> str:
+    """sha256 (16 hex digits) of the frame kernels' machine code in the library: every
+    instantiation of march_kernel, march_pair_kernel (lane groups: small row shares) and
+    order_tiles_kernel (the adaptive tile order inside a frame) -- gfx950 code bytes and kernel
+    descriptor (code_object_symbols).
+    Keys measured per-kernel figures (the PMC traffic bench.py's roofline reads) to the machine
+    code they were measured on: host-only edits and changes to other kernels leave it
+    unchanged, any change to a kernel a frame launches moves it (the build is deterministic;
+    ADVICE r5: the pair and tile-order kernels were not hashed before)."""
+    import hashlib
+    syms = [(name, code) for name, code in code_object_symbols(path)
+            if any(k in name for k in (b"12march_kernel", b"17march_pair_kernel",
+                                       b"18order_tiles_kernel"))]
     if not syms:
         raise RuntimeError(f"{path or LIB_PATH}: no march_kernel code in the gfx950 code object")
     h = hashlib.sha256()
@@ -799,6 +817,13 @@ def kernel_code_hash(path: Optional[str] = None) -> str:
         h.update(name)
         h.update(code)
     return h.hexdigest()[:16]
+
+
+def variant_name(**facts) -> Optional[str]:
+    """vr_debug_variant_name: the kernel a launch with these vr_variant_facts runs (None: none)."""
+    buf = C.create_string_buffer(256)
+    f = vr_variant_facts(**facts)
+    return buf.value.decode() if lib().vr_debug_variant_name(C.byref(f), buf, len(buf)) == 0 else None
 
 
 def shard_rows(height: int, row_block: int, nranks: int) -> int:
