@@ -57,6 +57,7 @@
 
 #include "vr.h"
 #include "vr_modes.h"
+#include "vr_iso.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -225,15 +226,25 @@ class BasicOffscreenPass {
         check(vr_set_transfer_function(ctx_, data.data(), (uint32_t)data.size()));
     }
 
-    // Extension (vr_modes.h): VR_MODE_COMPOSITE, the reference's composite, or VR_MODE_MIP,
-    // maximum-intensity projection, for the frames recorded from now on (a UI toggle calls it
-    // like slicing_changed)
+    // Extension (vr_modes.h): VR_MODE_COMPOSITE, the reference's composite, VR_MODE_MIP,
+    // maximum-intensity projection, or VR_MODE_ISO, the first-hit isosurface, for the frames
+    // recorded from now on (a UI toggle calls it like slicing_changed)
     void render_mode_changed(int mode) { check(vr_set_render_mode(ctx_, mode)); }
     int render_mode() const
     {
         int m = VR_MODE_COMPOSITE;
         vr_get_render_mode(ctx_, &m);
         return m;
+    }
+
+    // Extension (vr_iso.h): the density of the VR_MODE_ISO surface, in the volume's own units,
+    // for the frames recorded from now on (a UI slider calls it like slicing_changed)
+    void isovalue_changed(float v) { check(vr_set_isovalue(ctx_, v)); }
+    float isovalue() const
+    {
+        float v = 0.0f;
+        vr_get_isovalue(ctx_, &v);
+        return v;
     }
 
     // offscreen_pass.h:53-54: the presenter's sampler / view of the frame's image

@@ -42,8 +42,8 @@ enum vr_knob {
                                oblique copy, 3 the plain copy, 4 the stencil copy (29^3-cell
                                plain bricks with a 1-below / 2-above apron), whenever the
                                launch allows it (2, the retired z-pair sparse copy: EINVAL) */
-    VR_KNOB_MIP_INFLIGHT = 10 /* VR_MODE_MIP (vr_modes.h): samples of a ray whose loads are in
-                               flight together: 0 auto, 1, 2 or 4 (same bytes)             */
+    VR_KNOB_MIP_INFLIGHT = 10 /* VR_MODE_MIP and VR_MODE_ISO (vr_modes.h): samples of a ray whose
+                               loads are in flight together: 0 auto, 1, 2 or 4 (same bytes) */
 };
 
 /* Per-device timing of a context (ABI 7), so that a multi-GPU frame that runs slow names its
@@ -105,7 +105,7 @@ int vr_debug_get_knob(const vr_ctx *ctx, int knob, int *value);
  * | 0x20 / 0x100 / 0x200 the oblique / plain / stencil f32 copy), `mode` a vr_render_mode, the
  * flags 0 or 1 (skip: granted; field: the difference field is in place, field_half: in
  * binary16; pipeline: pipelining wanted), pair 0 or the lanes per ray, mip_inflight the MIP
- * samples in flight.  vr_debug_variant_name is pure (no context, no device): the demangled name
+ * or ISO samples in flight.  vr_debug_variant_name is pure (no context, no device): the demangled name
  * of the kernel such a launch runs, as a profiler reports it, into buf (n bytes, truncated);
  * VR_EINVAL where no kernel serves the facts (the launch would fail) or on a NULL argument. */
 typedef struct vr_variant_facts {

@@ -2,7 +2,7 @@
  * vr_modes.h — render modes of a context (an addition beside vr.h; VR_ABI_VERSION and
  * vr_params are unchanged).
  *
- * A context renders in one of two modes.  The mode is context state, like the slice box: it
+ * A context renders in one of three modes.  The mode is context state, like the slice box: it
  * applies to every frame issued after the call, through vr_render, vr_render_device (row shares
  * included), vr_prepare, vr_count_work, vr_timing_*, vr_kernel_name and vr_dist_render.
  *
@@ -10,6 +10,11 @@
  *                      (volume.frag), everything vr.h describes.
  *   VR_MODE_MIP        maximum-intensity projection: the pixel shows the largest density
  *                      sample of its ray, looked up in the transfer function once.
+ *   VR_MODE_ISO        first-hit isosurface: the first point of the ray whose density reaches
+ *                      the context's isovalue, drawn as a lit opaque surface (vr_iso.h has the
+ *                      isovalue's entry points and the semantics).
+ *
+ * The value 2 is unassigned: vr_set_render_mode refuses it like any unknown mode.
  *
  * MIP semantics.  The ray is the composite's: the same pixel ray and entry point, nsteps =
  * int(ray_dist / step), the position update p = p + dir * step in f32, the bounds break and the
@@ -54,7 +59,7 @@
 extern "C" {
 #endif
 
-enum vr_render_mode { VR_MODE_COMPOSITE = 0, VR_MODE_MIP = 1 };
+enum vr_render_mode { VR_MODE_COMPOSITE = 0, VR_MODE_MIP = 1, VR_MODE_ISO = 3 /* 2: unassigned */ };
 
 /* Set the mode of the frames issued from now on (frames already issued keep theirs; a
  * multi-device context forwards it to every device once its issued frames are done).

@@ -9,6 +9,7 @@
 #include "../../include/vr/vr.h"
 #include "../../include/vr/vr_debug.h"
 #include "../../include/vr/vr_modes.h"
+#include "../../include/vr/vr_iso.h"
 #include "vr_internal.h"
 #include "vr_group.h"
 
@@ -68,6 +69,7 @@ struct vr_ctx {
     float smin[3] = {0.0f, 0.0f, 0.0f};
     float smax[3] = {1.0f, 1.0f, 1.0f};
     int render_mode = VR_MODE_COMPOSITE;  // vr_modes.h: context state, like the slice box
+    float isovalue = 0.0f;                // vr_iso.h: context state, read in VR_MODE_ISO only
     // empty-space classification (skip_empty), built lazily: per-brick value range after a
     // volume change, the brick distance field after a volume or TF change
     float2 *brick_range = nullptr;
@@ -1137,6 +1139,37 @@ int mip_inflight(const vr_ctx *c, bool skip)
     return kMipDefaultInFlight;
 }
 
+// The same for the ISO kernel's search loop (vr_iso.h; the knob forces both), by measurement
+// (tools/iso_bench.py, profiles/r08/iso/; shaded, isovalue at 0.3 of the data range, ms per
+// frame, K = 1 / 2 / 4):
+//   8-bit yz-quads (C2): 4 (fill 0.224 / 0.201 / 0.198, default camera 0.119 / 0.106 / 0.099;
+//     with skipping 2 and 4 tie: 0.236 / 0.216 / 0.217 and 0.131 / 0.121 / 0.119);
+//   plain 8-bit bricks (C4): 4 without skipping (fill 0.986 / 0.807 / 0.796, default camera
+//     0.373 / 0.305 / 0.296), 2 with (0.867 / 0.772 / 0.960 and 0.309 / 0.279 / 0.344);
+//   f32 (C3): 4 without skipping (fill 0.385 / 0.295 / 0.282), 2 with (0.317 / 0.299 / 0.316);
+//     on sparse views (the default camera) as MIP: 1 without skipping (0.216 / 0.254 / 0.250)
+//     and 4 with (0.137 / 0.130 / 0.127);
+//   16-bit yz-quads: MIP's choice (not measured).
+// The isovalues at 0.15 and 0.6 of the range rank the same way, but for C3's default camera
+// without skipping at 0.15, where K = 4 (0.173) is ahead of K = 1 (0.187).
+int iso_inflight(const vr_ctx *c, bool skip)
+{
+    if (c->knobs.mip_inflight) return c->knobs.mip_inflight;
+    if (c->layout == ST_F32 && c->pixel_span > kAltSpan) return skip ? 4 : 1;
+    if (c->layout == ST_U16 || c->layout == ST_I16) return mip_inflight(c, skip);
+    if (c->layout & kQuadFlag) return 4;
+    return skip ? 2 : 4;
+}
+// MIP and ISO frames read the base bricks through ensure_mip and launch with these facts
+bool range_mode(const vr_ctx *c)
+{
+    return c->render_mode == VR_MODE_MIP || c->render_mode == VR_MODE_ISO;
+}
+IsoArgs iso_args(const vr_ctx *c, const vr_params *p, const MipArgs &M)
+{
+    return {M.brick_range, M.nbricks, c->isovalue, p->shading != 0};
+}
+
 // f32 frames of oblique views (the centre ray's direction less than kAltAlign along every axis)
 // read the kAltFlag copy (7x15x8-cell bricks), sparse axis-aligned views (more than kAltSpan
 // voxels per pixel step) the kWideFlag copy (15x15x8): their rows never straddle a 128-B line,
@@ -1254,15 +1287,18 @@ int ensure_alt(vr_ctx *c, int lay, hipStream_t s, bool *ready)
 VariantFacts launch_facts(const vr_ctx *c, const vr_params *p, const MarchParams &P, int layout,
                           bool count)
 {
-    const bool mip = c->render_mode == VR_MODE_MIP, skip = P.skip_empty != 0;  // skip: granted
+    const bool skip = P.skip_empty != 0;  // skip: granted
+    const int k = c->render_mode == VR_MODE_MIP   ? mip_inflight(c, skip)
+                  : c->render_mode == VR_MODE_ISO ? iso_inflight(c, skip)
+                                                  : 0;
     return {layout, c->render_mode, p->shading != 0, count, skip, P.grad != nullptr, P.grad_half,
-            P.pipelined, P.tf_n, P.pair, mip ? mip_inflight(c, skip) : 0};
+            P.pipelined, P.tf_n, P.pair, k};
 }
 // ... and the facts vr_kernel_name predicts from the context for the next full frame (vr.h:
 // row_block 16, one rank, a single lane per ray, the last view).  It cannot build anything,
 // so it differs from launch_facts where the launch would:
 //   skip   composite: as requested (the launch: as granted -- the memory budget may refuse the
-//          skip structures); MIP: only once the brick ranges are in place;
+//          skip structures); MIP and ISO: only once the brick ranges are in place;
 //   field  only once a shaded frame has built it (the launch builds it when the policy wants it);
 //   layout an alternative copy only once it exists (the launch builds it);
 //   pair   never (documented: the single-lane variant, also where the frame runs lane groups).
@@ -1273,9 +1309,9 @@ VariantFacts next_frame_facts(const vr_ctx *c, const vr_params *p)
     f.mode = c->render_mode;
     f.shade = p && p->shading;
     f.tf_n = (int32_t)c->tf_n;
-    if (f.mode == VR_MODE_MIP) {
+    if (range_mode(c)) {
         f.skip = p && p->skip_empty && c->range_valid && c->nbricks_alloc;
-        f.mip_inflight = mip_inflight(c, f.skip);
+        f.mip_inflight = f.mode == VR_MODE_ISO ? iso_inflight(c, f.skip) : mip_inflight(c, f.skip);
         return f;
     }
     f.skip = p && p->skip_empty;
@@ -2055,7 +2091,7 @@ int vr_set_slicing(vr_ctx *c, const float min_slice[3], const float max_slice[3]
 int vr_set_render_mode(vr_ctx *c, int mode)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP)
+    if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP && mode != VR_MODE_ISO)  // 2: unassigned
         return fail(c, VR_EINVAL, "unknown render mode");
     if (is_group(c)) {  // frames already issued keep the old mode (as the slice box)
         if (int rc = group_idle(c)) return rc;
@@ -2070,6 +2106,26 @@ int vr_get_render_mode(const vr_ctx *c, int *mode)
 {
     if (!c || !mode) return fail(nullptr, VR_EINVAL, "NULL argument");
     *mode = c->render_mode;
+    return VR_OK;
+}
+
+int vr_set_isovalue(vr_ctx *c, float v)
+{
+    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
+    if (!std::isfinite(v)) return fail(c, VR_EINVAL, "the isovalue is not finite");
+    if (is_group(c)) {  // frames already issued keep the old isovalue (as the mode)
+        if (int rc = group_idle(c)) return rc;
+        for (vr_ctx *m : c->members)
+            if (int rc = vr_set_isovalue(m, v)) return member_rc(c, m, rc);
+    }
+    c->isovalue = v;
+    return VR_OK;
+}
+
+int vr_get_isovalue(const vr_ctx *c, float *v)
+{
+    if (!c || !v) return fail(nullptr, VR_EINVAL, "NULL argument");
+    *v = c->isovalue;
     return VR_OK;
 }
 
@@ -2203,8 +2259,8 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
     uint32_t refused = 0;  // VR_DERIVED_* the budget or free memory refused this frame
     MipArgs M{nullptr, 0};
     int layout = c->layout;
-    const bool mip = c->render_mode == VR_MODE_MIP;
-    if (mip) {  // the base bricks and, with skip_empty, the brick ranges
+    const bool mip = range_mode(c);
+    if (mip) {  // MIP and ISO: the base bricks and, with skip_empty, the brick ranges
         rc = ensure_mip(c, p, P, M, s, &refused);
         if (rc) return rc;
     } else {
@@ -2250,7 +2306,8 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
         if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
         HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
     }
-    HIP_TRY(c, launch_frame(v, P, M, s), mip ? "mip kernel launch" : "march kernel launch");
+    HIP_TRY(c, launch_frame(v, P, M, iso_args(c, p, M), s),
+            v.family == VF_ISO ? "iso kernel launch" : mip ? "mip kernel launch" : "march kernel launch");
     c->last_variant = v;
     if (timing) {
         HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
@@ -2455,13 +2512,14 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
     if (rc) return rc;
     uint32_t refused = 0;  // a count is not a frame: not a downgrade
     MipArgs M{nullptr, 0};
-    const bool mip = c->render_mode == VR_MODE_MIP;
+    const bool mip = range_mode(c);
     rc = mip ? ensure_mip(c, p, P, M, nullptr, &refused) : ensure_derived(c, p, P, nullptr, &refused);
     if (rc) return rc;
     HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
     FrameVariant v;
     resolve_variant(launch_facts(c, p, P, c->layout, true), &v);
-    HIP_TRY(c, launch_frame(v, P, M, nullptr), mip ? "mip (count) launch" : "march (count) launch");
+    HIP_TRY(c, launch_frame(v, P, M, iso_args(c, p, M), nullptr),
+            v.family == VF_ISO ? "iso (count) launch" : mip ? "mip (count) launch" : "march (count) launch");
     c->last_variant = v;
     unsigned long long h[5];
     HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");

@@ -368,10 +368,21 @@ struct MipArgs {
     const float2 *brick_range;
     uint32_t nbricks;
 };
-// The kernel `v` names (resolve_variant) over p's tiles; m is read by mip_kernel alone.
-// hipErrorInvalidValue: no such kernel (variant_built), or MIP skipping without m.brick_range.
+// ---- First-hit isosurface (include/vr/vr_iso.h, iso_kernel) ----
+// What the ISO kernel reads beside MarchParams (its own argument, as MipArgs): the brick ranges
+// of MipArgs (null without range skipping), the isovalue in density units and vr_params.shading
+// (read once per ray: a run-time flag, not a template argument).
+struct IsoArgs {
+    const float2 *brick_range;
+    uint32_t nbricks;
+    float iso;
+    int32_t shading;
+};
+// The kernel `v` names (resolve_variant) over p's tiles; m is read by mip_kernel alone, i by
+// iso_kernel alone.  hipErrorInvalidValue: no such kernel (variant_built), or MIP / ISO
+// skipping without the brick ranges.
 hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
-                        hipStream_t stream);
+                        const IsoArgs &i, hipStream_t stream);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

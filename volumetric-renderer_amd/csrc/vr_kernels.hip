@@ -1610,6 +1610,247 @@ __global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams 
     }
 }
 
+// ---- first-hit isosurface (include/vr/vr_iso.h) ----------------------------------------------
+// The same ray as march_strip and mip_strip, but the pixel shows the first in-slab sample whose
+// density reaches the isovalue: a search with an ordered early exit, then -- once the whole
+// wavefront has left the search loop -- four bisection fetches between the last sample below
+// (q) and the hit, one gradient from the base bricks (the exact f32 central differences of
+// gradient<VT>, never the binary16 field) and the composite's Phong; the pixel is opaque.
+// The search loop is mip_strip's: K steps' loads are issued before any is filtered, lanes
+// whose ray has ended or whose sample is off-slab or skipped load element 0.  Unlike the
+// maximum the result depends on the order: the samples of a batch are examined in step order
+// behind a position cursor that repeats the ray's own additions, the hit is the lowest step
+// that passes, q the in-slab step before it (possibly of the previous batch), and what the
+// batch loaded beyond the hit is dropped.  So the frame is the same for every K.
+//
+// SKIP: a sample whose brick's stored maximum hi (widened for f32 as mip_strip's, by the same
+// argument: every sample in the brick is <= hi) is below the isovalue cannot hit and is not
+// fetched; it still counts as a sample below (prev, q).  !(hi < iso) keeps NaN bricks, and a
+// NaN sample never hits (d >= iso is false).
+// COUNT (K = 1, so a hit ends the lane before its next step is counted): rays, steps, search
+// samples fetched and skipped; shaded = rays whose surface point was shaded.  The bisection
+// fetches are not counted.
+template <typename VT, bool COUNT, bool SKIP, int K>
+__device__ __forceinline__ void iso_strip(const MarchParams &P, const IsoArgs &I, uint32_t tile_x,
+                                          uint32_t tile_y, uint32_t wave, uint32_t lane)
+{
+    static_assert(!COUNT || K == 1, "the counting kernels walk one step at a time");
+    using G = GeomOf<VT>;
+    const long by_stride = (long)P.nbx * G::Elems;  // elements between brick rows/slabs
+    const long bz_stride = (long)P.nbx * P.nby * G::Elems;
+    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
+    const uint32_t wpr = kTile >> ws;
+    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
+    const uint32_t px = tile_x * kTile + (wave % wpr) * ww + lx_;
+    const uint32_t ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
+    bool active = px < P.W && ly < P.local_rows;
+    const uint32_t blk = ly / P.row_block;
+    const uint32_t gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) *
+                            P.row_block + (ly - blk * P.row_block);
+    active = active && gy < P.H;
+
+    float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
+    const bool covered = active && pixel_ray(P, px, gy, tex, dir);
+
+    const float iso = I.iso;
+    bool hit = false, prev = false;
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f;  // the last in-slab position below the isovalue
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f;  // the hit
+    unsigned long long n_samples = 0, n_steps = 0, n_skipped = 0;
+    uint32_t cur_brick = 0xFFFFFFFFu;
+    float cur_hi = INFINITY;
+    const char *__restrict__ vol = static_cast<const char *>(P.vol);
+    const int nsteps = covered ? P.nsteps : 0;
+    float p0 = tex[0], p1 = tex[1], p2 = tex[2];
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
+
+    struct Stage {
+        MipRaw<VT> r;
+        float ax, ay, az;
+        bool live, slab, fetch, issued;
+    };
+    bool live = nsteps > 0;
+    for (int it = 0; live; it += K) {
+        Stage S[K];
+        float c0 = p0, c1 = p1, c2 = p2;  // the position of the step being examined
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const int k = it + s;
+            const bool interior = (unsigned)(k - 1) < (unsigned)kin;
+            // volume.frag:34-37: the first position outside ends the ray
+            live = live && k < nsteps &&
+                   (interior || !(p0 > 1.0f || p1 > 1.0f || p2 > 1.0f || p0 < 0.0f || p1 < 0.0f ||
+                                  p2 < 0.0f));
+            if (COUNT && live) ++n_steps;
+            // volume.frag:39-40 (strict)
+            const bool slab = live && (interior || (p0 < P.smax[0] && p1 < P.smax[1] &&
+                                                    p2 < P.smax[2] && p0 > P.smin[0] &&
+                                                    p1 > P.smin[1] && p2 > P.smin[2]));
+            int i, j, kk;
+            texel_coord(p0, P.fnx, i, S[s].ax);
+            texel_coord(p1, P.fny, j, S[s].ay);
+            texel_coord(p2, P.fnz, kk, S[s].az);
+            const int pi = i + kPad, pj = j + kPad, pk = kk + kPad;
+            bool fetch = slab;
+            if constexpr (SKIP) {
+                if (slab) {
+                    const uint32_t bb = ((uint32_t)pk / G::BZ * P.nby + (uint32_t)pj / G::BY) * P.nbx +
+                                        (uint32_t)pi / G::BX;
+                    if (bb != cur_brick) {
+                        cur_brick = bb;
+                        const float2 r = VR_OOB(7, bb, I.nbricks) ? make_float2(NAN, NAN)
+                                                                   : I.brick_range[bb];
+                        cur_hi = kZPair<VT> ? r.y + (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.y;
+                    }
+                    fetch = !(cur_hi < iso);
+                }
+            }
+            if (COUNT && slab) {
+                if (fetch)
+                    ++n_samples;
+                else
+                    ++n_skipped;
+            }
+            S[s].live = live;
+            S[s].slab = slab;
+            S[s].fetch = fetch;
+            size_t ce = fetch ? cell_offset<VT>(pi, pj, pk, P.nbx, P.nby) : (size_t)0;
+            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+            // without SKIP every step loads; with it a step no lane of the wave fetches does not
+            S[s].issued = !SKIP || __any(fetch);
+            if (S[s].issued) S[s].r.issue(vol, ce);
+            // volume.frag:47
+            p0 = p0 + d0 * P.step;
+            p1 = p1 + d1 * P.step;
+            p2 = p2 + d2 * P.step;
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            float d = 0.0f;
+            if (S[s].issued) {
+                Cell8<VT> c;
+                S[s].r.decode(c);
+                d = c.tri(S[s].ax, S[s].ay, S[s].az);
+            }
+            if (!hit && S[s].live) {
+                if (S[s].slab) {
+                    if (S[s].fetch && d >= iso) {
+                        hit = true;
+                        h0 = c0;
+                        h1 = c1;
+                        h2 = c2;
+                    } else {
+                        prev = true;
+                        q0 = c0;
+                        q1 = c1;
+                        q2 = c2;
+                    }
+                } else {
+                    prev = false;
+                }
+            }
+            c0 = c0 + d0 * P.step;
+            c1 = c1 + d1 * P.step;
+            c2 = c2 + d2 * P.step;
+        }
+        live = live && !hit;
+    }
+
+    const bool shade = hit && I.shading != 0;
+    if (COUNT) {
+        const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
+        const unsigned long long sm = wave_sum(n_samples);
+        const unsigned long long sh = wave_sum(shade ? 1ull : 0ull);
+        const unsigned long long st = wave_sum(n_steps);
+        const unsigned long long sk = wave_sum(n_skipped);
+        if (lane == 0) {
+            atomicAdd(&P.counters[0], rays);
+            atomicAdd(&P.counters[1], sm);
+            atomicAdd(&P.counters[2], sh);
+            atomicAdd(&P.counters[3], st);
+            atomicAdd(&P.counters[4], sk);
+        }
+    }
+    if (!active) return;
+
+    // no hit: the clear colour, with an uncovered pixel's arithmetic (T = 1, C = 0)
+    float o0 = 0.0f * 0.0f + P.clear[0] * 1.0f, o1 = 0.0f * 0.0f + P.clear[1] * 1.0f,
+          o2 = 0.0f * 0.0f + P.clear[2] * 1.0f, o3 = 0.0f * 0.0f + P.clear[3] * 1.0f;
+    if (hit) {
+        if (prev) {  // bisection between q (below) and the hit (at or above): in-slab by convexity
+#pragma unroll 1
+            for (int r = 0; r < 4; ++r) {
+                const float m0 = (q0 + h0) * 0.5f, m1 = (q1 + h1) * 0.5f, m2 = (q2 + h2) * 0.5f;
+                int i, j, kk;
+                float ax, ay, az;
+                texel_coord(m0, P.fnx, i, ax);
+                texel_coord(m1, P.fny, j, ay);
+                texel_coord(m2, P.fnz, kk, az);
+                size_t ce = cell_offset<VT>(i + kPad, j + kPad, kk + kPad, P.nbx, P.nby);
+                if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+                Cell8<VT> c;
+                c.load(vol, ce);
+                const bool above = c.tri(ax, ay, az) >= iso;
+                h0 = above ? m0 : h0;
+                h1 = above ? m1 : h1;
+                h2 = above ? m2 : h2;
+                q0 = above ? q0 : m0;
+                q1 = above ? q1 : m1;
+                q2 = above ? q2 : m2;
+            }
+        }
+        // the surface colour: the TF at the isovalue (alpha ignored), read through the global
+        // pointer once per ray
+        const float tt = div_by_range(iso - P.vmin, P);
+        float4 s = tf_lookup(P.tf, P.tf_n, P.tf_nf, tt);
+        if (shade) {
+            int i, j, kk;
+            float ax, ay, az;
+            texel_coord(h0, P.fnx, i, ax);
+            texel_coord(h1, P.fny, j, ay);
+            texel_coord(h2, P.fnz, kk, az);
+            const int pi = i + kPad, pj = j + kPad, pk = kk + kPad;
+            size_t ce = cell_offset<VT>(pi, pj, pk, P.nbx, P.nby);
+            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+            Cell8<VT> c;
+            c.load(vol, ce);
+            float gx, gy_, gz;
+            gradient<VT, false>(vol, ce, c, pi, pj, pk, P.nbx, P.nby, by_stride, bz_stride, ax, ay,
+                                az, gx, gy_, gz);
+            phong(P, gx, gy_, gz, d0, d1, d2, s);
+        }
+        o0 = s.x;
+        o1 = s.y;
+        o2 = s.z;
+        o3 = 1.0f;
+    }
+    const size_t idx = (size_t)ly * P.W + px;
+    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
+    if (P.out_format == 0) {
+        static_cast<uint32_t *>(P.out)[idx] =
+            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
+    } else {
+        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
+    }
+}
+
+template <typename VT, bool COUNT, bool SKIP, int K>
+__global__ __launch_bounds__(kThreadsPerTile) void iso_kernel(const MarchParams P, const IsoArgs I)
+{
+    const int tid = threadIdx.x;
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    const long long wg_start = wall_clock64();
+    iso_strip<VT, COUNT, SKIP, K>(P, I, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
+        __syncthreads();
+        if (tid == 0)
+            P.tile_cost[tile_y * P.tiles_x + tile_x] =
+                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
+    }
+}
+
 // ---- lane-pair march (small launches) ----------------------------------------------------------
 // Two lanes per ray: lane 0 of the pair fetches, filters and shades the even samples, lane 1 the
 // odd ones; both keep the ray position with the same float additions (p_(k+1) = p_k + d step,
@@ -2342,10 +2583,12 @@ constexpr uint32_t march_lds_pad() { return 0; }
 using VariantTypes = std::tuple<uint8_t, int8_t, uint16_t, int16_t, float, Quad8<uint8_t>,
                                 Quad8<int8_t>, F32Alt, F32H, F32P, F32S>;
 static_assert(std::tuple_size<VariantTypes>::value == kVariantTags, "one type per VariantTag");
-using FrameLauncher = void (*)(uint32_t nblocks, const MarchParams &, const MipArgs &, hipStream_t);
+using FrameLauncher = void (*)(uint32_t nblocks, const MarchParams &, const MipArgs &, const IsoArgs &,
+                               hipStream_t);
 
 template <int I>
-void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, hipStream_t stream)
+void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, const IsoArgs &iso,
+                 hipStream_t stream)
 {
     constexpr FrameVariant v = variant_at(I);
     using VT = std::tuple_element_t<v.tag, VariantTypes>;
@@ -2355,9 +2598,12 @@ void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, hipSt
     else if constexpr (v.family == VF_PAIR)
         hipLaunchKernelGGL((march_pair_kernel<VT, v.shade, v.gf, v.lanes>), dim3(nblocks),
                            dim3(kThreads), 0, stream, p);
-    else
+    else if constexpr (v.family == VF_MIP)
         hipLaunchKernelGGL((mip_kernel<VT, v.count, v.skip, v.inflight>), dim3(nblocks),
                            dim3(kThreadsPerTile), 0, stream, p, m);
+    else
+        hipLaunchKernelGGL((iso_kernel<VT, v.count, v.skip, v.inflight>), dim3(nblocks),
+                           dim3(kThreadsPerTile), 0, stream, p, iso);
 }
 
 template <int I>
@@ -2432,17 +2678,19 @@ hipError_t brick_from(const void *src, void *dst, uint32_t nx, uint32_t ny, uint
 }  // namespace
 
 hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
-                        hipStream_t stream)
+                        const IsoArgs &iso, hipStream_t stream)
 {
     static constexpr auto launchers = slot_launchers(std::make_integer_sequence<int, kVariantSlots>{});
     const int i = variant_index(v);
     const FrameLauncher fn = i >= 0 && i < kVariantSlots ? launchers[(size_t)i] : nullptr;
-    if (!fn || (v.family == VF_MIP && v.skip && !m.brick_range)) return hipErrorInvalidValue;
+    if (!fn || (v.family == VF_MIP && v.skip && !m.brick_range) ||
+        (v.family == VF_ISO && v.skip && !iso.brick_range))
+        return hipErrorInvalidValue;
     if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
     const uint32_t nblocks = p.tile_perm ? p.nperm
                              : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
                                                  : p.tiles_x * p.tiles_y;
-    fn(nblocks, p, m, stream);
+    fn(nblocks, p, m, iso, stream);
     return hipGetLastError();
 }
 

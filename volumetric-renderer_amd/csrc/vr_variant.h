@@ -1,12 +1,12 @@
 // vr_variant.h — which kernel a launch runs, stated once.
 //
-// A frame (or a vr_count_work pass) runs one instantiation of march_kernel, march_pair_kernel
-// or mip_kernel: a FrameVariant.  resolve_variant is the only place the mapping from a launch's
-// resolved inputs (VariantFacts) to it is written, variant_built the only list of the
+// A frame (or a vr_count_work pass) runs one instantiation of march_kernel, march_pair_kernel,
+// mip_kernel or iso_kernel: a FrameVariant.  resolve_variant is the only place the mapping from
+// a launch's resolved inputs (VariantFacts) to it is written, variant_built the only list of the
 // instantiations the library carries; the launch (launch_frame, vr_kernels.hip), the name a
 // profiler reports and the tile-schedule key all derive from the one FrameVariant.  The policy
 // -- which facts a view gets -- is not here (use_pipeline, use_grad_field, use_pair, want_alt,
-// mip_inflight in vr_api.hip).  Plain C++17, no HIP types.
+// mip_inflight, iso_inflight in vr_api.hip).  Plain C++17, no HIP types.
 #pragma once
 
 #include <stdint.h>
@@ -24,7 +24,7 @@ enum StorageType { ST_U8 = 0, ST_I8 = 1, ST_U16 = 2, ST_I16 = 3, ST_F32 = 4 };
 constexpr int kQuadFlag = 0x10, kAltFlag = 0x20, kPlainF32Flag = 0x100, kStencilF32Flag = 0x200;
 constexpr int kTfLds = 256;  // TF texels staged in LDS (lane groups and pipelining need it there)
 
-enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2 };
+enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2, VF_ISO = 3 };
 // The kernels' storage type tag (their first template argument): kTagNames and launch_frame's
 // type list follow this order.  TAG_F32H: the ST_F32 bricks read with the binary16 field.
 enum VariantTag {
@@ -36,8 +36,9 @@ constexpr const char *kTagNames[kVariantTags] = {
     "vr::Quad8<unsigned char>", "vr::Quad8<signed char>", "vr::F32Alt", "vr::F32H", "vr::F32P",
     "vr::F32S"};
 
-// march_kernel<VT, shade, count, skip, gf, pipe>, march_pair_kernel<VT, shade, gf, lanes> or
-// mip_kernel<VT, count, skip, inflight>; what a family does not take stays false / 0.
+// march_kernel<VT, shade, count, skip, gf, pipe>, march_pair_kernel<VT, shade, gf, lanes>,
+// mip_kernel<VT, count, skip, inflight> or iso_kernel<VT, count, skip, inflight>; what a family
+// does not take stays false / 0.
 struct FrameVariant {
     int family = VF_NONE, tag = 0;
     bool shade = false, count = false, skip = false, gf = false, pipe = false;
@@ -61,10 +62,11 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
                     : f.layout == (ST_F32 | kPlainF32Flag)   ? TAG_F32P
                     : f.layout == (ST_F32 | kStencilF32Flag) ? TAG_F32S
                                                              : -1;
-    if (f.mode == VR_MODE_MIP) {  // base layouts only: MIP reads no alternative copy
+    if (f.mode == VR_MODE_MIP || f.mode == VR_MODE_ISO) {  // base layouts only: no alternative copy
         const int k = f.count ? 1 : f.mip_inflight;  // the counting kernels walk step by step
         if (base < 0 || (k != 1 && k != 2 && k != 4)) return false;
-        *v = {VF_MIP, base, false, f.count != 0, f.skip != 0, false, false, 0, k};
+        *v = {f.mode == VR_MODE_ISO ? VF_ISO : VF_MIP, base, false, f.count != 0, f.skip != 0, false,
+              false, 0, k};
         return true;
     }
     // an alternative copy carries no skip-empty structures, field or lane groups, and no counts
@@ -79,7 +81,8 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
     return true;
 }
 
-// The instantiations the library carries: 92 march_kernel, 32 march_pair_kernel, 56 mip_kernel.
+// The instantiations the library carries: 92 march_kernel, 32 march_pair_kernel, 56 mip_kernel,
+// 56 iso_kernel.
 constexpr bool variant_built(const FrameVariant &v)
 {
     const bool alt = v.tag == TAG_F32ALT || v.tag == TAG_F32P || v.tag == TAG_F32S;
@@ -89,15 +92,16 @@ constexpr bool variant_built(const FrameVariant &v)
     switch (v.family) {
         case VF_MARCH: return !(v.pipe && (v.count || v.skip)) && !(alt && (v.count || v.skip));
         case VF_PAIR: return !alt && (v.lanes == 2 || v.lanes == 4);
-        case VF_MIP: return !alt && (v.inflight == 1 || (!v.count && (v.inflight == 2 || v.inflight == 4)));
+        case VF_MIP:
+        case VF_ISO: return !alt && (v.inflight == 1 || (!v.count && (v.inflight == 2 || v.inflight == 4)));
         default: return false;
     }
 }
 
 // A dense numbering of every (family, tag, flags) combination, built or not: launch_frame's
 // table index and the variant part of the tile-schedule key.  5 flag bits: march shade, count,
-// skip, gf, pipe; pair shade, gf, 4 lanes; mip count, skip, log2(inflight) (2 bits).
-constexpr int kVariantSlots = 3 * kVariantTags * 32;
+// skip, gf, pipe; pair shade, gf, 4 lanes; mip and iso count, skip, log2(inflight) (2 bits).
+constexpr int kVariantSlots = 4 * kVariantTags * 32;
 constexpr int variant_index(const FrameVariant &v)
 {
     const int k = v.inflight == 1 ? 0 : v.inflight == 2 ? 1 : v.inflight == 4 ? 2 : 3;
@@ -128,8 +132,9 @@ inline std::string variant_kernel_name(const FrameVariant &v)
     if (v.family == VF_PAIR)
         return ns + "march_pair_kernel<" + vt + b(v.shade) + b(v.gf) + ", " +
                std::to_string(v.lanes) + ">(vr::MarchParams)";
-    return ns + "mip_kernel<" + vt + b(v.count) + b(v.skip) + ", " + std::to_string(v.inflight) +
-           ">(vr::MarchParams, vr::MipArgs)";
+    return ns + (v.family == VF_ISO ? "iso_kernel<" : "mip_kernel<") + vt + b(v.count) + b(v.skip) +
+           ", " + std::to_string(v.inflight) +
+           (v.family == VF_ISO ? ">(vr::MarchParams, vr::IsoArgs)" : ">(vr::MarchParams, vr::MipArgs)");
 }
 
 // The adaptive tile order's schedule key: tile durations differ by kernel and by the copy it

@@ -9,7 +9,9 @@
 //   vr_cli <file.nhdr|file.nrrd|synthetic:N> <out.ppm> [--size WxH] [--radius R]
 //          [--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS]
 //          [--skip-empty] [--frames K] [--device-mask M]   (M: render every frame across these GPUs)
-//          [--mode composite|mip]   (mip: maximum-intensity projection, include/vr/vr_modes.h)
+//          [--mode composite|mip|iso]   (mip: maximum-intensity projection, include/vr/vr_modes.h;
+//                                        iso: first-hit isosurface, include/vr/vr_iso.h)
+//          [--iso V]   (the isosurface's density, in the volume's units; default 0)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -25,13 +27,13 @@ int main(int argc, char **argv)
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <file.nhdr|synthetic:N> <out.ppm> [--size WxH] [--radius R] "
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
-                             "[--frames K] [--device-mask M] [--mode composite|mip]\n",
+                             "[--frames K] [--device-mask M] [--mode composite|mip|iso] [--iso V]\n",
                      argv[0]);
         return 2;
     }
     std::string src = argv[1], out = argv[2];
     uint32_t W = 800, H = 600;
-    float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f;
+    float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
     std::string tfname = "default", mode = "composite";
@@ -46,6 +48,7 @@ int main(int argc, char **argv)
         else if (a == "--skip-empty") skip_empty = 1;
         else if (a == "--ert" && i + 1 < argc) ert = std::strtof(argv[++i], nullptr);
         else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
+        else if (a == "--iso" && i + 1 < argc) iso = std::strtof(argv[++i], nullptr);
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -53,7 +56,7 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (mode != "composite" && mode != "mip") {
+    if (mode != "composite" && mode != "mip" && mode != "iso") {
         std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
         return 2;
     }
@@ -95,7 +98,10 @@ int main(int argc, char **argv)
         Vol::Rendering::Hip::Camera cam{};
         vr_cam_view(&oc, cam.view);
         vr_cam_position(&oc, cam.position);
-        pass.render_mode_changed(mode == "mip" ? VR_MODE_MIP : VR_MODE_COMPOSITE);
+        pass.render_mode_changed(mode == "mip"   ? VR_MODE_MIP
+                                 : mode == "iso" ? VR_MODE_ISO
+                                                 : VR_MODE_COMPOSITE);
+        pass.isovalue_changed(iso);  // state: read by iso frames only
         pass.params().shading = shading;
         pass.params().exact_gradient = exact_gradient;
         pass.params().skip_empty = skip_empty;

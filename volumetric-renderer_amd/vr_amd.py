@@ -131,6 +131,9 @@ DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_memb
 # include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
 MODE_COMPOSITE, MODE_MIP = 0, 1
+MODE_ISO = 3  # (2 is unassigned and refused)
+# include/vr/vr_iso.h: the isovalue of VR_MODE_ISO (context state)
+ISO_SYMBOLS = ["vr_set_isovalue", "vr_get_isovalue"]
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -219,6 +222,8 @@ def lib() -> C.CDLL:
         "vr_debug_get_knob": (i32, [vp, i32, C.POINTER(i32)]),
         "vr_set_render_mode": (i32, [vp, i32]),
         "vr_get_render_mode": (i32, [vp, C.POINTER(i32)]),
+        "vr_set_isovalue": (i32, [vp, C.c_float]),
+        "vr_get_isovalue": (i32, [vp, C.POINTER(C.c_float)]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
@@ -530,7 +535,8 @@ class OffscreenPass:
                     "transfer_function_changed")
 
     def render_mode_changed(self, mode: int):
-        """vr_set_render_mode (vr_modes.h): MODE_COMPOSITE or MODE_MIP for the frames that follow."""
+        """vr_set_render_mode (vr_modes.h): MODE_COMPOSITE, MODE_MIP or MODE_ISO for the frames
+        that follow."""
         self._check(lib().vr_set_render_mode(self._ctx, int(mode)), "render_mode_changed")
 
     @property
@@ -538,6 +544,16 @@ class OffscreenPass:
         m = C.c_int()
         self._check(lib().vr_get_render_mode(self._ctx, C.byref(m)), "vr_get_render_mode")
         return int(m.value)
+
+    def isovalue_changed(self, v: float):
+        """vr_set_isovalue (vr_iso.h): the MODE_ISO surface's density, in the volume's units."""
+        self._check(lib().vr_set_isovalue(self._ctx, C.c_float(v)), "isovalue_changed")
+
+    @property
+    def isovalue(self) -> float:
+        v = C.c_float()
+        self._check(lib().vr_get_isovalue(self._ctx, C.byref(v)), "vr_get_isovalue")
+        return float(v.value)
 
     # -- record/render --
     def render(self, camera: OrbitCamera, params: Optional[vr_params] = None,
