@@ -323,7 +323,8 @@ typedef struct vr_memory_info {
     uint64_t plain_copy_bytes;    /* plain 15^3-cell copy (unshaded sparse views)      */
     uint64_t stencil_copy_bytes;  /* 29^3-cell stencil copy (shaded sparse views)      */
     uint64_t skip_bytes;          /* skip-empty brick ranges + distance field          */
-    uint64_t derived_bytes;       /* the sum of the five above: what the budget caps   */
+    uint64_t derived_bytes;       /* the sum of the five above and of the y-major copy
+                                     (vr_debug.h): what the budget caps                 */
     uint64_t budget_bytes;        /* the budget in force, in bytes (the default's value
                                      for this volume; VR_MEMORY_BUDGET_UNLIMITED)       */
     /* (ABI 9) history since the context was created */
@@ -338,7 +339,10 @@ enum vr_derived {
     VR_DERIVED_OBLIQUE_COPY = 2,   /* 7x15x8-cell z-pair copy     */
     VR_DERIVED_PLAIN_COPY = 3,     /* plain 15^3-cell copy        */
     VR_DERIVED_STENCIL_COPY = 4,   /* stencil copy                */
-    VR_DERIVED_SKIP = 5            /* skip-empty classification   */
+    VR_DERIVED_SKIP = 5,           /* skip-empty classification   */
+    VR_DERIVED_YMAJOR_COPY = 6     /* y-major copy (dense-row views along y): counted only when
+                                      forced (vr_debug.h knob); left to the policy it is built
+                                      into spare budget alone and its absence is no downgrade */
 };
 #define VR_MEMORY_BUDGET_UNLIMITED (~(uint64_t)0)
 #define VR_MEMORY_BUDGET_DEFAULT (~(uint64_t)0 - 1)

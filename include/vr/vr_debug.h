@@ -40,7 +40,9 @@ enum vr_knob {
                                stencil copy when shaded, a plain one-voxel-per-element 15^3
                                one when not), 0 never, 1 the
                                oblique copy, 3 the plain copy, 4 the stencil copy (29^3-cell
-                               plain bricks with a 1-below / 2-above apron), whenever the
+                               plain bricks with a 1-below / 2-above apron), 5 the y-major
+                               copy (y-pair elements, y slowest in a brick; auto: dense-row
+                               views along y of volumes beyond 256 MiB of bricks), whenever the
                                launch allows it (2, the retired z-pair sparse copy: EINVAL) */
     VR_KNOB_MIP_INFLIGHT = 10 /* VR_MODE_MIP and VR_MODE_ISO (vr_modes.h): samples of a ray whose
                                loads are in flight together: 0 auto, 1, 2 or 4 (same bytes) */
@@ -102,7 +104,8 @@ int vr_debug_get_knob(const vr_ctx *ctx, int knob, int *value);
 /* Which kernel a launch runs (csrc/vr_variant.h is the statement of the
  * table).  vr_variant_facts mirrors the resolved inputs of that decision: `layout` is the
  * layout code of the copy read (vr_debug_volume_info's storage code, | 0x10 8-bit yz-quads,
- * | 0x20 / 0x100 / 0x200 the oblique / plain / stencil f32 copy), `mode` a vr_render_mode, the
+ * | 0x20 / 0x100 / 0x200 / 0x400 the oblique / plain / stencil / y-major f32 copy), `mode` a
+ * vr_render_mode, the
  * flags 0 or 1 (skip: granted; field: the difference field is in place, field_half: in
  * binary16; pipeline: pipelining wanted), pair 0 or the lanes per ray, mip_inflight the MIP
  * or ISO samples in flight.  vr_debug_variant_name is pure (no context, no device): the demangled name
@@ -119,6 +122,12 @@ int vr_debug_variant_name(const vr_variant_facts *facts, char *buf, size_t n);
  * frame.  A multi-device context answers for member 0; "" before any launch.  The string is
  * valid until the calling thread's next call. */
 const char *vr_debug_last_kernel_name(const vr_ctx *ctx);
+
+/* Bytes the y-major copy of an f32 volume takes now on the (first) device, 0 when absent (dense-row
+ * views along y of volumes beyond the Infinity Cache read it).  It counts in
+ * vr_memory_info.derived_bytes like every derived structure; the ABI 9 struct has no field of
+ * its own for it. */
+uint64_t vr_debug_ymajor_copy_bytes(const vr_ctx *ctx);
 
 #ifdef __cplusplus
 }

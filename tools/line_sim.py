@@ -159,32 +159,6 @@ def tile_shapes(n=512, ntiles=60):
             print(f"{cname:13s} {lname:10s} lines/sample: " + "  ".join(row), flush=True)
 
 
-if __name__ == "__main__":
-    sys.path.insert(0, os.path.join(ROOT, "volumetric-renderer_amd"))
-    import synth
-    if len(sys.argv) > 1 and sys.argv[1] == "tiles":
-        tile_shapes()
-        sys.exit(0)
-    n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
-    cams = {"fill": synth.camera("fill"), "fill_oblique": synth.camera("fill_oblique"),
-            "side_x": synth.vr_amd.make_camera(radius=1.6, rotate=(360.0, 0.0)),
-            "top_z": synth.vr_amd.make_camera(radius=1.6, rotate=(0.0, 360.0))}
-    layouts = {
-        "brick16+apron f32 (current, dwordx2)": (brick_apron(16, 4), 4),
-        "brick8+apron f32 (dwordx2)": (brick_apron(8, 4), 4),
-        "brick4+apron f32 (dwordx2)": (brick_apron(4, 4), 4),
-        "brick16+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(16, 4), 4),
-        "brick8+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(8, 4), 4),
-        "brick4+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(4, 4), 4),
-    }
-    for cname, cam in cams.items():
-        vc = cam.to_vr_camera()
-        for lname, (fn, vb) in layouts.items():
-            r = simulate(fn, n, vb, list(vc.view), list(vc.position), ntiles=60)
-            print(f"{cname:13s} {lname:40s} lines/instr {r['lines_per_instr']:6.2f}  "
-                  f"lines/sample {r['lines_per_sample']:.3f}")
-
-
 # ---- plain 8-bit layouts (round 2: cutting the yz-quad's 4x duplication) --------------------
 def brick_plain_u8(B, pad_to=4):
     """u8 voxels one per element in (B+1)^3-element bricks (apron), brick stride rounded up to
@@ -349,6 +323,56 @@ def zpair_geom(BX, BY, BZ, vb=4):
     return fn
 
 
+def ypair_geom(BX=8, BY=8, BZ=8, vb=4):
+    """f32 y-pairs in the y-major copy (vr_internal.h F32Y): elements x + EX (z + EZ y) in a
+    brick, the bricks in the same order; a sample = 2 x 16-B loads at e and e + EX (rows z, z + 1)."""
+    EX, EY, EZ = BX + 1, BY + 1, BZ + 1
+
+    def fn(i, j, k, nb):
+        pi, pj, pk = i + 2, j + 2, k + 2
+        b = ((pk // BZ) * nb + (pj // BY)) * nb + (pi // BX)
+        base = (b * EX * EY * EZ + ((pj % BY) * EZ + (pk % BZ)) * EX + (pi % BX)) * 2 * vb
+        return [(base, 4 * vb), (base + EX * 2 * vb, 4 * vb)]
+    return fn
+
+
+def frame_lines(view_name, layout, n=512, W=1920, H=1080, line=128, rows_per_pass=30):
+    """Distinct `line`-byte lines of `layout` one whole frame touches: every pixel's ray, every
+    step (no early termination, the reference-equivalent sample count), the kernel's cell
+    addressing and loads.  The compulsory DRAM traffic of a frame whose volume does not stay in
+    the caches is these lines, once: the figure a layout has to cut for a view before any
+    counter can show it (C3, r = 1.6 axis-aligned views: z-pair bricks with the ray along y
+    1.336 GB, along z 0.825 GB; the y-major copy turns the former into the latter)."""
+    sys.path.insert(0, os.path.join(ROOT, "volumetric-renderer_amd"))
+    import synth
+    cams = {"side_x": dict(radius=1.6, rotate=(360.0, 0.0)), "top_z": dict(radius=1.6, rotate=(0.0, 360.0))}
+    vc = (synth.vr_amd.make_camera(**cams[view_name]) if view_name in cams
+          else synth.camera(view_name)).to_vr_camera()
+    view, pos = list(vc.view), list(vc.position)
+    nb = (n + 3) // 4 + 1
+    top = (nb ** 3) * 9 ** 3 * 8 // line + 2
+    seen = np.zeros(top, dtype=bool)
+    samples = 0
+    for y0 in range(0, H, rows_per_pass):
+        px, py = np.meshgrid(np.arange(W), np.arange(y0, min(H, y0 + rows_per_pass)))
+        ok, pos0, dirs = rays(view, pos, W, H, px.ravel().astype(float), py.ravel().astype(float))
+        p = np.clip(pos0[ok], 0.0, 1.0)  # the entry-face snap (pixel_ray)
+        d = dirs[ok]
+        for _ in range(360):
+            inb = np.all((p >= 0) & (p <= 1), axis=1)
+            if not inb.any():
+                break
+            p, d = p[inb], d[inb]
+            i0 = np.floor(p * n - 0.5).astype(np.int64)
+            for addr, width in layout(i0[:, 0], i0[:, 1], i0[:, 2], nb):
+                seen[addr // line] = True
+                seen[(addr + width - 1) // line] = True
+            samples += len(p)
+            p = p + d * 0.005
+    lines = int(seen.sum())
+    return dict(view=view_name, samples=samples, lines=lines, bytes=lines * line)
+
+
 def tile_box_model(view_name="fill", n=512, W=1920, H=1080, K=8, ntiles=40, seed=1):
     """Cells in the box a 16x16-pixel tile's rays sample over a stage of K steps (the LDS
     staging a tile-stage would need): median / p90 / max over stages."""
@@ -376,3 +400,39 @@ def tile_box_model(view_name="fill", n=512, W=1920, H=1080, K=8, ntiles=40, seed
             sizes.append(float(np.prod(u.max(0) + 1 - u.min(0) + 1)))
     s = np.array(sizes)
     return dict(K=K, median=float(np.median(s)), p90=float(np.percentile(s, 90)), max=float(s.max()))
+
+
+if __name__ == "__main__":
+    sys.path.insert(0, os.path.join(ROOT, "volumetric-renderer_amd"))
+    import synth
+    if len(sys.argv) > 1 and sys.argv[1] == "tiles":
+        tile_shapes()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "frame":
+        # frame [n]: distinct line bytes per C3-geometry frame, z-pair bricks against the
+        # y-major copy, rays along y (fill) and along z (top_z)
+        n = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+        for vname in ("fill", "top_z"):
+            for lname, fn in (("z-pair 8^3", zpair_geom(8, 8, 8)), ("y-major 8^3", ypair_geom())):
+                r = frame_lines(vname, fn, n)
+                print(f"{vname:6s} {lname:12s} samples {r['samples'] / 1e6:7.1f} M  distinct lines "
+                      f"{r['lines'] / 1e6:6.2f} M = {r['bytes'] / 1e9:.3f} GB", flush=True)
+        sys.exit(0)
+    n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
+    cams = {"fill": synth.camera("fill"), "fill_oblique": synth.camera("fill_oblique"),
+            "side_x": synth.vr_amd.make_camera(radius=1.6, rotate=(360.0, 0.0)),
+            "top_z": synth.vr_amd.make_camera(radius=1.6, rotate=(0.0, 360.0))}
+    layouts = {
+        "brick16+apron f32 (current, dwordx2)": (brick_apron(16, 4), 4),
+        "brick8+apron f32 (dwordx2)": (brick_apron(8, 4), 4),
+        "brick4+apron f32 (dwordx2)": (brick_apron(4, 4), 4),
+        "brick16+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(16, 4), 4),
+        "brick8+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(8, 4), 4),
+        "brick4+apron f32 zpair (dwordx4 x2)": (brick_apron_zpair(4, 4), 4),
+    }
+    for cname, cam in cams.items():
+        vc = cam.to_vr_camera()
+        for lname, (fn, vb) in layouts.items():
+            r = simulate(fn, n, vb, list(vc.view), list(vc.position), ntiles=60)
+            print(f"{cname:13s} {lname:40s} lines/instr {r['lines_per_instr']:6.2f}  "
+                  f"lines/sample {r['lines_per_sample']:.3f}")

@@ -54,7 +54,7 @@ def load(d, kname):
 
 def main():
     d = sys.argv[1]
-    kname = sys.argv[2] if len(sys.argv) > 2 else "march_kernel"
+    kname = sys.argv[2] if len(sys.argv) > 2 else "march_"
     c, dur = load(d, kname)
     out = {"kernel_substr": kname, "counters": c, "profiled_dispatch_s": dur}
     g = lambda k: c.get(k)

@@ -40,7 +40,7 @@ CONFIGS = ("c3", "c3_ref", "c3_default", "c2", "c4", "c5")
 
 def frame_kernel(name):
     """True for a march launch that renders a frame (not the COUNT instantiation)."""
-    for k in ("march_kernel<", "march_pair_kernel<", "march_lds_kernel<"):
+    for k in ("march_kernel<", "march_pair_kernel<", "march_lds_kernel<", "march_y_kernel<"):
         if k in name:
             targs = template_args(name, k)
             return not (k == "march_kernel<" and targs[2] == "true")  # <VT, SHADE, COUNT, ...>

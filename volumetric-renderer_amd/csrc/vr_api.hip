@@ -52,14 +52,15 @@ struct vr_ctx {
     int ray_axis = 2;         // the volume axis of that component (0 x, 1 y, 2 z)
     double row_align = 1.0;   // |x component| of the unit pixel step along the image x axis
     // f32 volumes: further resident copies in the alternative geometries (kAltFlag for
-    // oblique views, the plain and stencil copies for sparse ones), each built lazily on the
-    // first frame that wants it after a volume change
+    // oblique views, the plain and stencil copies for sparse ones, the y-major copy for
+    // dense-row views along y), each built lazily on the first frame that wants it after a
+    // volume change
     struct AltCopy {
         void *bricks = nullptr;  // stream-ordered allocation (hipMallocAsync)
         size_t bytes = 0;
         bool valid = false, failed = false;
         uint64_t used = 0;  // frame_no of the latest frame that read it (eviction order)
-    } alt[3];
+    } alt[4];
     uint32_t nx = 1, ny = 1, nz = 1;
     float vmin = 0.0f, vmax = 1.0f;
     // transfer function (decoded, linear float RGBA)
@@ -654,7 +655,8 @@ bool use_pipeline(bool shading, uint32_t tiles, const vr_ctx *c)
 // stay faster single-lane (tools/shard_sweep.py, profiles/r01/multi_gpu/).  Serial frames
 // only (vr_params.frames_in_flight <= 1).  Not for
 // skip-empty frames or TFs beyond the LDS copy.  Knob VR_KNOB_PAIR 0/1 overrides (A/B).
-int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field);
+int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field, bool field_half,
+             bool pipelined);
 bool use_pair(const vr_ctx *c, const MarchParams &P, const vr_params *p)
 {
     if (p->skip_empty || P.tf_n > kTfLds) return false;
@@ -674,7 +676,8 @@ bool use_pair(const vr_ctx *c, const MarchParams &P, const vr_params *p)
     if (c->knobs.alt >= 0 || c->layout != ST_F32 || c->dense_rows || c->pixel_span <= kAltSpan ||
         (c->ray_axis == 2 && c->axis_align >= kAltAlign))
         return false;
-    return want_alt(c, p, P.pair != 0, P.grad != nullptr) == (ST_F32 | kAltFlag);
+    return want_alt(c, p, P.pair != 0, P.grad != nullptr, P.grad_half != 0, P.pipelined != 0) ==
+           (ST_F32 | kAltFlag);
 }
 
 int build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
@@ -877,6 +880,7 @@ int release_async(vr_ctx *c, void *p, hipStream_t s)
     HIP_TRY(c, hipFreeAsync(p, s), "hipFreeAsync(derived structure)");
     return VR_OK;
 }
+constexpr int kYMajorAlt = 3;  // alt_index of the y-major copy
 // Evict derived structures, least recently read first, until `extra` more bytes (replacing
 // `replaced` bytes of the same structure) fit the budget; never the copy `keep_alt` (alt index,
 // or -1) the frame reads, nor the field when `keep_field`.  Returns VR_OK with *fits.
@@ -885,7 +889,7 @@ int make_room(vr_ctx *c, size_t extra, size_t replaced, int keep_alt, bool keep_
 {
     *fits = budget_allows(c, extra, replaced);
     while (!*fits) {
-        int pick = -2;  // -1 the field, 0..2 an alternative copy
+        int pick = -2;  // -1 the field, 0..3 an alternative copy
         uint64_t oldest = ~0ull;
         if (c->grad && !keep_field && c->grad_used < oldest) {
             pick = -1;
@@ -896,6 +900,9 @@ int make_room(vr_ctx *c, size_t extra, size_t replaced, int keep_alt, bool keep_
                 pick = i;
                 oldest = c->alt[i].used;
             }
+        // the y-major copy goes first, whatever its age: its views lose 5-6 per cent without it
+        // (DESIGN.md §8), every other structure's views more (want_alt)
+        if (keep_alt != kYMajorAlt && c->alt[kYMajorAlt].bricks) pick = kYMajorAlt;
         if (pick == -2) return VR_OK;  // nothing left to evict: does not fit
         if (pick == -1) {
             if (int rc = release_async(c, c->grad, s)) return rc;
@@ -1197,9 +1204,38 @@ IsoArgs iso_args(const vr_ctx *c, const vr_params *p, const MipArgs &M)
 // bricks on every view whose ray runs along x.  So, off the dense-row views: sparse views along
 // the rows take the plain / stencil copy; axis-aligned views with the ray along y or z and at
 // most kAltSpan voxels per pixel keep the 8^3 bricks; every other view reads the oblique copy.
-int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field)
+// Dense-row views whose ray runs along y (the frame-filling camera, the reference's default
+// orbit) read the y-major copy (kYMajorFlag; vr_internal.h F32Y): in the z-pair bricks each of
+// their 2.56-voxel steps reads rows y and y + 1 of every z-layer, nearly every line of the
+// volume; y-major, a step passes whole y-layers by (0.62x the distinct lines per frame,
+// tools/line_sim.py frame).  It is the one copy read together with the difference field, which
+// stays z-major (shaded frames: the binary16 field only).  Its kernels exist in the pipelined
+// single-lane form alone, so: no lane groups, skip-empty or counting, the TF within the LDS
+// copy.  Auto, only with every launch-policy knob at its default and only for bricks beyond the
+// 256 MiB Infinity Cache -- a smaller volume is cache-resident and has no line traffic to save.
+// It never evicts another structure (ensure_alt) and is the first one evicted (make_room).
+// Knob VR_KNOB_ALT_GEOMETRY 5: every eligible launch, at any size.
+constexpr size_t kInfinityCacheBytes = 256ull << 20;
+bool knobs_default(const vr_ctx *c)
 {
-    if (c->layout != ST_F32 || p->skip_empty || pair || field) return c->layout;
+    const vr_ctx::Knobs &k = c->knobs;
+    return k.pipeline < 0 && k.pair < 0 && k.pair_lanes == 0 && k.grad_field < 0 && k.alt < 0 &&
+           k.tile_order == 0;
+}
+bool want_ymajor(const vr_ctx *c, const vr_params *p, bool field, bool field_half, bool pipelined)
+{
+    if (!pipelined || c->tf_n > (uint32_t)kTfLds) return false;
+    if (p->shading ? !(field && field_half && p->exact_gradient == 0) : field) return false;
+    if (c->knobs.alt >= 0) return c->knobs.alt == 5;
+    return knobs_default(c) && c->dense_rows && c->ray_axis == 1 &&
+           c->brick_bytes > kInfinityCacheBytes;
+}
+int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field, bool field_half,
+             bool pipelined)
+{
+    if (c->layout != ST_F32 || p->skip_empty || pair) return c->layout;
+    if (want_ymajor(c, p, field, field_half, pipelined)) return ST_F32 | kYMajorFlag;
+    if (field) return c->layout;  // the other copies carry no field
     int which = 0;
     if (c->knobs.alt >= 0)
         which = c->knobs.alt;
@@ -1222,7 +1258,14 @@ int want_alt(const vr_ctx *c, const vr_params *p, bool pair, bool field)
 int alt_index(int layout)
 {
     if (layout & kAltFlag) return 0;
+    if (layout & kYMajorFlag) return kYMajorAlt;
     return (layout & kPlainF32Flag) ? 1 : 2;
+}
+// the VR_DERIVED_* code of the copy in layout `layout` (vr_memory_info.last_downgrade)
+uint32_t alt_derived_code(int layout)
+{
+    return (layout & kYMajorFlag) ? (uint32_t)VR_DERIVED_YMAJOR_COPY
+                                  : (uint32_t)(VR_DERIVED_OBLIQUE_COPY + alt_index(layout));
 }
 
 // Bytes of the copy of the current volume in layout `lay`.
@@ -1252,8 +1295,11 @@ int ensure_alt(vr_ctx *c, int lay, hipStream_t s, bool *ready)
         // over the budget: the least recently read other copies, then the field (read only by
         // dense-row views, never by a frame that reads a copy), make room; else this frame reads
         // the 8^3 bricks (same pixels)
+        // (the y-major copy evicts nothing: it is built only into room the budget has left)
         bool fits = false;
-        if (int rc = make_room(c, bytes + kBrickSlackBytes, had, alt_index(lay), false, s, &fits))
+        if (lay & kYMajorFlag)
+            fits = budget_allows(c, bytes + kBrickSlackBytes, had);
+        else if (int rc = make_room(c, bytes + kBrickSlackBytes, had, alt_index(lay), false, s, &fits))
             return rc;
         if (!fits) return VR_OK;
         if (int rc = release_async(c, a.bricks, s)) return rc;
@@ -1319,8 +1365,8 @@ VariantFacts next_frame_facts(const vr_ctx *c, const vr_params *p)
     f.field_half = f.field && p->exact_gradient == 0;
     const uint32_t tiles = ((c->width + 15) / 16) * ((c->height + kMarchRows - 1) / kMarchRows);
     f.pipeline = use_pipeline(f.shade, tiles, c);
-    if (p && !f.field)
-        if (const int lay = want_alt(c, p, false, false);
+    if (p)
+        if (const int lay = want_alt(c, p, false, f.field != 0, f.field_half != 0, f.pipeline != 0);
             lay != c->layout && c->alt[alt_index(lay)].valid)
             f.layout = lay;
     return f;
@@ -1490,7 +1536,7 @@ bool knob_value_ok(int knob, int v)
     switch (knob) {
         case VR_KNOB_PAIR_LANES: return v == 0 || v == 2 || v == 4;
         case VR_KNOB_NARROW: return v == 0 || v == 1;
-        case VR_KNOB_ALT_GEOMETRY: return v >= -1 && v <= 4 && v != 2;
+        case VR_KNOB_ALT_GEOMETRY: return v >= -1 && v <= 5 && v != 2;
         case VR_KNOB_TILE_ORDER: return v >= 0 && v <= 4;
         case VR_KNOB_MIP_INFLIGHT: return v == 0 || v == 1 || v == 2 || v == 4;
         default: return v >= -1 && v <= 1;
@@ -2275,7 +2321,10 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
             P.supers_total = P.supers_x * ((P.tiles_y + kSuper - 1) / kSuper);
         }
         // oblique and sparse f32 views: an alternative-geometry copy (want_alt)
-        if (const int lay = want_alt(c, p, P.pair != 0, P.grad != nullptr); lay != c->layout) {
+        // (and the y-major copy, the one copy a frame reads beside the difference field)
+        if (const int lay = want_alt(c, p, P.pair != 0, P.grad != nullptr, P.grad_half != 0,
+                                     P.pipelined != 0);
+            lay != c->layout) {
             bool ready = false;
             rc = ensure_alt(c, lay, s, &ready);
             if (rc) return rc;
@@ -2286,7 +2335,10 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
                 P.nbx = bricks_for(c->nx, 0, layout);
                 P.nby = bricks_for(c->ny, 1, layout);
             } else {
-                refused = (uint32_t)(VR_DERIVED_OBLIQUE_COPY + alt_index(lay));
+                // the y-major copy is opportunistic (it evicts nothing, so under a full budget
+                // it is often absent): the frame then runs what it ran before the copy existed,
+                // which is no downgrade unless the caller forced the copy (knob 5)
+                if (!(lay & kYMajorFlag) || c->knobs.alt == 5) refused = alt_derived_code(lay);
             }
         }
     }
@@ -2679,6 +2731,14 @@ const char *vr_debug_last_kernel_name(const vr_ctx *c)
     thread_local std::string name;
     name = variant_kernel_name(c->last_variant);
     return name.c_str();
+}
+
+uint64_t vr_debug_ymajor_copy_bytes(const vr_ctx *c)
+{
+    if (!c) return 0;
+    if (is_group(c)) return vr_debug_ymajor_copy_bytes(c->members[0]);
+    const vr_ctx::AltCopy &a = c->alt[kYMajorAlt];
+    return a.bricks ? a.bytes + kBrickSlackBytes : 0;
 }
 
 int vr_debug_set_knob(vr_ctx *c, int knob, int value)

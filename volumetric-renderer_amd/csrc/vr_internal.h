@@ -88,7 +88,7 @@ constexpr int kGroupShift = VR_BRICK_GROUP_SHIFT;
 constexpr uint32_t kGroupMask = (1u << kGroupShift) - 1;
 
 // Bits 0..g-1 of v moved to bits 0, 3, 6, ... (one axis of a Morton code).
-__host__ __device__ __forceinline__ uint32_t morton_spread(uint32_t v)
+__host__ __device__ __forceinline__ constexpr uint32_t morton_spread(uint32_t v)
 {
     uint32_t r = 0;
 #pragma unroll
@@ -97,8 +97,9 @@ __host__ __device__ __forceinline__ uint32_t morton_spread(uint32_t v)
 }
 
 // Memory slot of brick (bx, by, bz) of an nbx x nby x * grid (whole groups per axis).
-__host__ __device__ __forceinline__ uint32_t brick_slot(uint32_t bx, uint32_t by, uint32_t bz,
-                                                        uint32_t nbx, uint32_t nby)
+__host__ __device__ __forceinline__ constexpr uint32_t brick_slot(uint32_t bx, uint32_t by,
+                                                                  uint32_t bz, uint32_t nbx,
+                                                                  uint32_t nby)
 {
     if constexpr (kGroupShift == 0) {
         return (bz * nby + by) * nbx + bx;
@@ -194,6 +195,84 @@ struct F32S {
 struct F32H {
     float v;
 };
+// The y-major copy (kYMajorFlag, kernel tags F32Y and, read with the binary16 field, F32HY): the
+// GeomWide brick grid in brick_slot order, but every element a y-pair {v(x,y,z), v(x,y+1,z)} and
+// the elements of a brick ordered x + EX (z + EZ y) -- y slowest.  A sample is 2 x 16-B loads at
+// e and e + EX (elements x, x + 1 of rows z and z + 1).  For dense-row views whose ray runs along
+// y: a step of 2.56 voxels then passes whole 648-B y-layers by, where in the z-pair bricks it
+// reads rows y and y + 1 of every z-layer, i.e. nearly every line.  The
+// difference field stays z-major and shared: a cell's field element is at ymajor_field_delta
+// elements from its y-major one.
+struct F32Y {
+    float v;
+};
+struct F32HY {
+    float v;
+};
+// Local element indices of padded cell (pi, pj, pk) inside its GeomWide brick: z-major (the
+// ST_F32 bricks, the field) and y-major (the copy).
+__host__ __device__ constexpr uint32_t zmajor_local(uint32_t xl, uint32_t yl, uint32_t zl)
+{
+    return xl + (uint32_t)GeomWide::EX * (yl + (uint32_t)GeomWide::EY * zl);
+}
+__host__ __device__ constexpr uint32_t ymajor_local(uint32_t xl, uint32_t yl, uint32_t zl)
+{
+    return xl + (uint32_t)GeomWide::EX * (zl + (uint32_t)GeomWide::EZ * yl);
+}
+// zmajor_local - ymajor_local (8^3 cells: 72 (zl - yl))
+__host__ __device__ constexpr int ymajor_field_delta(uint32_t yl, uint32_t zl)
+{
+    return GeomWide::EX * (GeomWide::BY * (int)zl - GeomWide::BZ * (int)yl);
+}
+// Element index of padded cell (pi, pj, pk) in the y-major copy; *field_delta (when not null):
+// what to add to reach the same cell's element in the z-major layout.
+__host__ __device__ constexpr size_t ymajor_cell_offset(uint32_t pi, uint32_t pj, uint32_t pk,
+                                                        uint32_t nbx, uint32_t nby,
+                                                        int *field_delta = nullptr)
+{
+    using G = GeomWide;
+    const uint32_t bx = pi / G::BX, by = pj / G::BY, bz = pk / G::BZ;
+    const uint32_t xl = pi - bx * G::BX, yl = pj - by * G::BY, zl = pk - bz * G::BZ;
+    if (field_delta) *field_delta = ymajor_field_delta(yl, zl);
+    return (size_t)brick_slot(bx, by, bz, nbx, nby) * (size_t)G::Elems + ymajor_local(xl, yl, zl);
+}
+namespace ymajor_check {
+// Over a 3 x 2 x 2-brick grid: every element (cells and apron) of every brick maps into its own
+// brick's [0, 729) exactly once, and the z-major index is the y-major one + the field delta.
+constexpr bool map_ok()
+{
+    using G = GeomWide;
+    constexpr uint32_t nbx = (3 + kGroupMask) & ~kGroupMask, nby = (2 + kGroupMask) & ~kGroupMask,
+                       nbz = nby;
+    for (uint32_t bz = 0; bz < nbz; ++bz)
+        for (uint32_t by = 0; by < nby; ++by)
+            for (uint32_t bx = 0; bx < nbx; ++bx) {
+                bool seen[G::EX * G::EY * G::EZ] = {};
+                const size_t base = (size_t)brick_slot(bx, by, bz, nbx, nby) * (size_t)G::Elems;
+                for (uint32_t zl = 0; zl < (uint32_t)G::EZ; ++zl)
+                    for (uint32_t yl = 0; yl < (uint32_t)G::EY; ++yl)
+                        for (uint32_t xl = 0; xl < (uint32_t)G::EX; ++xl) {
+                            const uint32_t l = ymajor_local(xl, yl, zl);
+                            if (l >= (uint32_t)(G::EX * G::EY * G::EZ) || seen[l]) return false;
+                            seen[l] = true;
+                            if ((int)zmajor_local(xl, yl, zl) - (int)l != ymajor_field_delta(yl, zl))
+                                return false;
+                            // cells (not the apron) through the kernels' addressing
+                            if (xl < (uint32_t)G::BX && yl < (uint32_t)G::BY && zl < (uint32_t)G::BZ) {
+                                int fd = 0;
+                                const size_t e = ymajor_cell_offset(bx * G::BX + xl, by * G::BY + yl,
+                                                                    bz * G::BZ + zl, nbx, nby, &fd);
+                                if (e != base + l || fd != ymajor_field_delta(yl, zl)) return false;
+                            }
+                        }
+            }
+    return true;
+}
+static_assert(map_ok(), "the y-major map is a bijection onto each brick, 72 (zl - yl) from z-major");
+static_assert(GeomWide::BX != 8 || GeomWide::BY != 8 || GeomWide::BZ != 8 ||
+                  ymajor_field_delta(3, 5) == 72 * (5 - 3),
+              "8^3 cells: l_zmajor - l_ymajor == 72 (zl - yl)");
+}  // namespace ymajor_check
 
 // Bytes of one voxel of storage type (or layout code) st.
 inline size_t storage_size(int st)
@@ -458,7 +537,8 @@ constexpr size_t kGradElemBytes = 24;
 hipError_t launch_grad_field(const float *bricks, float *grad, uint32_t nx, uint32_t ny,
                              uint32_t nz, bool half, int scale_log2, hipStream_t stream);
 // The f32 copy in layout `storage` (kAltFlag / kPlainF32Flag / kStencilF32Flag) straight from the
-// 8^3 z-pair bricks: the same bytes as launch_unbrick + launch_brick_from_linear.
+// 8^3 z-pair bricks: the same bytes as launch_unbrick + launch_brick_from_linear.  kYMajorFlag:
+// the y-major copy (F32Y above), one pass of its own over the same bricks.
 hipError_t launch_rebrick_f32(const float *src_bricks, void *dst, uint32_t nx, uint32_t ny,
                               uint32_t nz, int storage, hipStream_t stream);
 // The binary16 field's scale: the largest k in [-120, 120] with B 2^k <= 65504, where

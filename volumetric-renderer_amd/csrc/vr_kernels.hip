@@ -105,14 +105,25 @@ template <>
 struct VoxOf<F32S> {
     using type = float;
 };
+template <>
+struct VoxOf<F32Y> {
+    using type = float;
+};
+template <>
+struct VoxOf<F32HY> {
+    using type = float;
+};
 template <typename VT>
 using Vox = typename VoxOf<VT>::type;
 template <typename VT>
 constexpr bool kIsQuad8 = is_quad8<VT>::value;
 // the f32 volume read with the binary16 difference field (MarchParams::grad_half)
 template <typename VT>
-constexpr bool kHalfField = std::is_same<VT, F32H>::value;
-// f32 z-pair elements (8^3 bricks, or GeomAlt bricks for F32Alt)
+constexpr bool kHalfField = std::is_same<VT, F32H>::value || std::is_same<VT, F32HY>::value;
+// the y-major copy (vr_internal.h F32Y): y-pair elements, a brick's elements y-slowest
+template <typename VT>
+constexpr bool kYMajor = std::is_same<VT, F32Y>::value || std::is_same<VT, F32HY>::value;
+// f32 pair elements: z-pairs (8^3 bricks, or GeomAlt bricks for F32Alt) or, kYMajor, y-pairs
 template <typename VT>
 constexpr bool kZPair = std::is_same<Vox<VT>, float>::value;
 // f32 voxels one per element (the F32P copy, or every f32 volume in VR_F32_PLAIN builds)
@@ -153,6 +164,7 @@ __device__ __forceinline__ size_t cell_offset(int pi, int pj, int pk, uint32_t n
 {
     using G = GeomOf<VT>;
     const uint32_t ux = (uint32_t)pi, uy = (uint32_t)pj, uz = (uint32_t)pk;
+    if constexpr (kYMajor<VT>) return ymajor_cell_offset(ux, uy, uz, nbx, nby);
     const uint32_t bx = ux / G::BX, by = uy / G::BY, bz = uz / G::BZ;
     const uint32_t l = ((uz - bz * G::BZ + G::Lo) * G::EY + (uy - by * G::BY + G::Lo)) * G::EX +
                        (ux - bx * G::BX + G::Lo);
@@ -265,7 +277,7 @@ struct CellRaw {  // generic: the decoded cell itself (loaded and decoded togeth
 };
 template <typename VT>
 struct CellRaw<VT, std::enable_if_t<kZPair<VT> && !kPlainF32<VT>>> {
-    f4a r0, r1;  // rows y and y + 1: elements x, x + 1 as z-pairs
+    f4a r0, r1;  // rows y and y + 1: elements x, x + 1 as z-pairs (kYMajor: rows z, z + 1, y-pairs)
 };
 template <typename VT>
 struct CellRaw<VT, std::enable_if_t<kStencilWide<VT>>> {
@@ -297,7 +309,7 @@ struct Cell8 : CellTaps<VT> {
     {
         if constexpr (kZPair<VT> && !kPlainF32<VT>) {
             w.r0 = zpair_load2(base, e);
-            w.r1 = zpair_load2(base, e + GeomOf<VT>::Row);
+            w.r1 = zpair_load2(base, e + GeomOf<VT>::Row);  // (kYMajor: the row at z + 1)
         } else if constexpr (kStencilWide<VT>) {
             using G = GeomOf<VT>;
 #pragma unroll
@@ -318,7 +330,16 @@ struct Cell8 : CellTaps<VT> {
     }
     __device__ __forceinline__ void decode(const CellRaw<VT> &w)
     {
-        if constexpr (kZPair<VT> && !kPlainF32<VT>) {
+        if constexpr (kYMajor<VT>) {  // r0 = row z, r1 = row z + 1; .xy / .zw = y-pairs at x / x + 1
+            v[0] = w.r0.x;
+            v[2] = w.r0.y;
+            v[1] = w.r0.z;
+            v[3] = w.r0.w;
+            v[4] = w.r1.x;
+            v[6] = w.r1.y;
+            v[5] = w.r1.z;
+            v[7] = w.r1.w;
+        } else if constexpr (kZPair<VT> && !kPlainF32<VT>) {
             v[0] = w.r0.x;
             v[4] = w.r0.y;
             v[1] = w.r0.z;
@@ -352,7 +373,7 @@ struct Cell8 : CellTaps<VT> {
     }
     __device__ __forceinline__ void load(const char *__restrict__ base, size_t e)
     {
-        if constexpr (kStencilWide<VT>) {
+        if constexpr (kStencilWide<VT> || kYMajor<VT>) {
             CellRaw<VT> w;
             issue(w, base, e);
             decode(w);
@@ -1136,7 +1157,7 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
         // The TF is LDS-resident (host guarantees tf_n <= kTfLds for PIPE).
         struct Stage {
             CellRaw<VT> w;  // loaded words, decoded at consume
-            size_t ce;
+            size_t ce;      // the cell's element (kYMajor: in the z-major layout, the field's)
             float ax, ay, az;
             int pi, pj, pk;
             bool ok, slab;
@@ -1158,9 +1179,21 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
             S.pi = i + kPad;
             S.pj = j + kPad;
             S.pk = kk + kPad;
-            S.ce = cell_offset<VT>(S.pi, S.pj, S.pk, P.nbx, P.nby);
-            if (VR_OOB(3, S.ce * kElemBytes<VT>, P.vol_bytes)) S.ce = 0;
-            Cell8<VT>::issue(S.w, vol, S.ce);
+            if constexpr (kYMajor<VT>) {
+                // the stage keeps the z-major element, where the shared difference field has
+                // this cell; the y-major one, that many elements before it, only issues the
+                // loads (no register beyond the z-pair kernels')
+                S.ce = cell_offset<float>(S.pi, S.pj, S.pk, P.nbx, P.nby);
+                size_t e = (size_t)((long)S.ce -
+                                    ymajor_field_delta((uint32_t)S.pj % (uint32_t)G::BY,
+                                                       (uint32_t)S.pk % (uint32_t)G::BZ));
+                if (VR_OOB(3, e * kElemBytes<VT>, P.vol_bytes)) e = S.ce = 0;
+                Cell8<VT>::issue(S.w, vol, e);
+            } else {
+                S.ce = cell_offset<VT>(S.pi, S.pj, S.pk, P.nbx, P.nby);
+                if (VR_OOB(3, S.ce * kElemBytes<VT>, P.vol_bytes)) S.ce = 0;
+                Cell8<VT>::issue(S.w, vol, S.ce);
+            }
         };
         auto composite = [&](const float4 &sm) -> bool {  // volume.frag:44-45
             cr = cr + (sm.x * sm.w) * T;
@@ -1394,6 +1427,37 @@ __global__ __launch_bounds__(kThreadsPerTile, (kMarchMinWaves<COUNT, SKIP, GF, P
     __syncthreads();
     if (tid == 0) wg_times_record((unsigned long long)wg_start, tile_y * P.tiles_x + tile_x);
 #endif
+}
+
+
+// The y-major copy's kernels (VT = F32Y unshaded, F32HY shaded with the binary16 field): the
+// pipelined single-lane march_strip over y-pair bricks.  A family of its own, so that
+// march_kernel's instantiations stay those of its own layout list (vr_variant.h).
+// The shaded one at a floor of 6 waves per SIMD: 80 VGPRs without scratch, as the F32H kernel
+// takes unconstrained (unconstrained, this one takes 84 and drops to 5 waves).
+template <typename VT, bool SHADE>
+__global__ __launch_bounds__(kThreadsPerTile, (SHADE ? 6 : kMarchMinWaves<false, false, false, true>)) void march_y_kernel(const MarchParams P)
+{
+    static_assert(kYMajor<VT> && kHalfField<VT> == SHADE, "F32Y unshaded, F32HY shaded");
+    __shared__ float4 s_tf[kTfLut];  // as march_kernel's
+    const int tid = threadIdx.x;
+
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    const long long wg_start = wall_clock64();
+
+    const bool tf_in_lds = P.tf_n <= kTfLds;  // (always: the host grants PIPE no other TF)
+    if (tf_in_lds)
+        for (int i = tid; i < 2 * (P.tf_n + 2); i += (int)kThreadsPerTile) s_tf[i] = P.tf[i];
+    __syncthreads();
+    march_strip<VT, SHADE, false, false, SHADE, true>(P, (LdsF4 *)s_tf, tf_in_lds, tile_x, tile_y,
+                                                      (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
+        __syncthreads();
+        if (tid == 0)
+            P.tile_cost[tile_y * P.tiles_x + tile_x] =
+                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
+    }
 }
 
 // ---- maximum-intensity projection (include/vr/vr_modes.h) ------------------------------------
@@ -2316,6 +2380,32 @@ __global__ __launch_bounds__(256) void rebrick_f32_kernel(const float *__restric
     }
 }
 
+// The y-major copy (vr_internal.h F32Y) from the 8^3 z-pair bricks: the same brick grid, one
+// thread per stored element, {v(x, y, z), v(x, y + 1, z)} read as padded_voxel -- the y + 1 voxel
+// of a brick's top layer from the neighbour brick, 0 outside the volume.
+__global__ __launch_bounds__(256) void rebrick_ymajor_kernel(const float *__restrict__ src,
+                                                             float2 *__restrict__ dst, uint32_t nx,
+                                                             uint32_t ny, uint32_t nz, uint32_t nbx,
+                                                             uint32_t nby, size_t nbricks)
+{
+    using G = GeomWide;
+    for (size_t bidx = blockIdx.x; bidx < nbricks; bidx += gridDim.x) {
+        uint32_t bx, by, bz;
+        brick_coords((uint32_t)bidx, nbx, nby, bx, by, bz);
+        for (uint32_t l = threadIdx.x; l < (uint32_t)G::Elems; l += blockDim.x) {
+            const uint32_t lx = l % G::EX, lzy = l / G::EX, lz = lzy % G::EZ, ly = lzy / G::EZ;
+            float2 v = make_float2(0.0f, 0.0f);  // (and the brick's alignment padding)
+            if (ly < (uint32_t)G::EY) {
+                const int x = (int)(bx * G::BX + lx), y = (int)(by * G::BY + ly),
+                          z = (int)(bz * G::BZ + lz);
+                v = make_float2(padded_voxel(src, x, y, z, nx, ny, nz, nbx, nby),
+                                padded_voxel(src, x, y + 1, z, nx, ny, nz, nbx, nby));
+            }
+            dst[bidx * G::Elems + l] = v;
+        }
+    }
+}
+
 // binary16 of d * 2^k (scale = 2^k): clamped to +-65504 first (NaN passes), rounded to nearest
 // even (v_cvt_f16_f32; f16 denormals kept).  The oracle's round_f16 restates it.
 __device__ __forceinline__ _Float16 field_half(float d, float scale)
@@ -2581,7 +2671,7 @@ constexpr uint32_t march_lds_pad() { return 0; }
 // launcher per variant slot -- null where the library carries no such kernel (variant_built),
 // so exactly the instantiations listed there exist.
 using VariantTypes = std::tuple<uint8_t, int8_t, uint16_t, int16_t, float, Quad8<uint8_t>,
-                                Quad8<int8_t>, F32Alt, F32H, F32P, F32S>;
+                                Quad8<int8_t>, F32Alt, F32H, F32P, F32S, F32Y, F32HY>;
 static_assert(std::tuple_size<VariantTypes>::value == kVariantTags, "one type per VariantTag");
 using FrameLauncher = void (*)(uint32_t nblocks, const MarchParams &, const MipArgs &, const IsoArgs &,
                                hipStream_t);
@@ -2595,6 +2685,9 @@ void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, const
     if constexpr (v.family == VF_MARCH)
         hipLaunchKernelGGL((march_kernel<VT, v.shade, v.count, v.skip, v.gf, v.pipe>), dim3(nblocks),
                            dim3(kThreadsPerTile), march_lds_pad(), stream, p);
+    else if constexpr (v.family == VF_MARCH_Y)
+        hipLaunchKernelGGL((march_y_kernel<VT, v.shade>), dim3(nblocks), dim3(kThreadsPerTile),
+                           march_lds_pad(), stream, p);
     else if constexpr (v.family == VF_PAIR)
         hipLaunchKernelGGL((march_pair_kernel<VT, v.shade, v.gf, v.lanes>), dim3(nblocks),
                            dim3(kThreads), 0, stream, p);
@@ -2839,6 +2932,7 @@ hipError_t launch_rebrick_f32(const float *src_bricks, void *dst, uint32_t nx, u
         case ST_F32 | kAltFlag: hipLaunchKernelGGL((rebrick_f32_kernel<F32Alt>), dim3(grid_bricks(total)), dim3(256), 0, s, src_bricks, d, nx, ny, nz, snbx, snby, snbz, nbx, nby, total); break;
         case ST_F32 | kPlainF32Flag: hipLaunchKernelGGL((rebrick_f32_kernel<F32P>), dim3(grid_bricks(total)), dim3(256), 0, s, src_bricks, d, nx, ny, nz, snbx, snby, snbz, nbx, nby, total); break;
         case ST_F32 | kStencilF32Flag: hipLaunchKernelGGL((rebrick_f32_kernel<F32S>), dim3(grid_bricks(total)), dim3(256), 0, s, src_bricks, d, nx, ny, nz, snbx, snby, snbz, nbx, nby, total); break;
+        case ST_F32 | kYMajorFlag: hipLaunchKernelGGL(rebrick_ymajor_kernel, dim3(grid_bricks(total)), dim3(256), 0, s, src_bricks, reinterpret_cast<float2 *>(d), nx, ny, nz, snbx, snby, total); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

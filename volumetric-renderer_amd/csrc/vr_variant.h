@@ -1,7 +1,7 @@
 // vr_variant.h — which kernel a launch runs, stated once.
 //
 // A frame (or a vr_count_work pass) runs one instantiation of march_kernel, march_pair_kernel,
-// mip_kernel or iso_kernel: a FrameVariant.  resolve_variant is the only place the mapping from
+// mip_kernel, iso_kernel or march_y_kernel: a FrameVariant.  resolve_variant is the only place the mapping from
 // a launch's resolved inputs (VariantFacts) to it is written, variant_built the only list of the
 // instantiations the library carries; the launch (launch_frame, vr_kernels.hip), the name a
 // profiler reports and the tile-schedule key all derive from the one FrameVariant.  The policy
@@ -19,26 +19,31 @@
 namespace vr {
 
 // Layout codes (the layouts themselves: vr_internal.h).  A base layout is a storage type, or
-// an 8-bit one | kQuadFlag; an alternative f32 copy is ST_F32 | one of the three copy flags.
+// an 8-bit one | kQuadFlag; an alternative f32 copy is ST_F32 | one of the four copy flags.
 enum StorageType { ST_U8 = 0, ST_I8 = 1, ST_U16 = 2, ST_I16 = 3, ST_F32 = 4 };
-constexpr int kQuadFlag = 0x10, kAltFlag = 0x20, kPlainF32Flag = 0x100, kStencilF32Flag = 0x200;
+constexpr int kQuadFlag = 0x10, kAltFlag = 0x20, kPlainF32Flag = 0x100, kStencilF32Flag = 0x200,
+              kYMajorFlag = 0x400;
 constexpr int kTfLds = 256;  // TF texels staged in LDS (lane groups and pipelining need it there)
 
-enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2, VF_ISO = 3 };
+enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2, VF_ISO = 3, VF_MARCH_Y = 4 };
+constexpr int kVariantFamilies = 5;
 // The kernels' storage type tag (their first template argument): kTagNames and launch_frame's
 // type list follow this order.  TAG_F32H: the ST_F32 bricks read with the binary16 field.
+// TAG_F32Y / TAG_F32HY: the y-major copy (kYMajorFlag), unshaded / shaded with the binary16
+// field; march_y_kernel's only tags, and no other family takes them.
 enum VariantTag {
     TAG_U8, TAG_I8, TAG_U16, TAG_I16, TAG_F32, TAG_QUAD_U8, TAG_QUAD_I8,
-    TAG_F32ALT, TAG_F32H, TAG_F32P, TAG_F32S, kVariantTags
+    TAG_F32ALT, TAG_F32H, TAG_F32P, TAG_F32S, TAG_F32Y, TAG_F32HY, kVariantTags
 };
 constexpr const char *kTagNames[kVariantTags] = {
     "unsigned char", "signed char", "unsigned short", "short", "float",
     "vr::Quad8<unsigned char>", "vr::Quad8<signed char>", "vr::F32Alt", "vr::F32H", "vr::F32P",
-    "vr::F32S"};
+    "vr::F32S", "vr::F32Y", "vr::F32HY"};
 
 // march_kernel<VT, shade, count, skip, gf, pipe>, march_pair_kernel<VT, shade, gf, lanes>,
-// mip_kernel<VT, count, skip, inflight> or iso_kernel<VT, count, skip, inflight>; what a family
-// does not take stays false / 0.
+// mip_kernel<VT, count, skip, inflight>, iso_kernel<VT, count, skip, inflight> or
+// march_y_kernel<VT, shade> (the pipelined single-lane march, gf = shade); what a family does
+// not take stays false / 0.
 struct FrameVariant {
     int family = VF_NONE, tag = 0;
     bool shade = false, count = false, skip = false, gf = false, pipe = false;
@@ -62,6 +67,16 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
                     : f.layout == (ST_F32 | kPlainF32Flag)   ? TAG_F32P
                     : f.layout == (ST_F32 | kStencilF32Flag) ? TAG_F32S
                                                              : -1;
+    if (f.layout == (ST_F32 | kYMajorFlag)) {
+        // the y-major copy: composite frames, pipelined, one lane per ray, TF in LDS; shaded
+        // ones read the shared binary16 field, unshaded ones none
+        if (f.mode != VR_MODE_COMPOSITE || f.count || f.pair || f.skip || !f.pipeline ||
+            f.tf_n > kTfLds || (f.shade ? !(f.field && f.field_half) : f.field != 0))
+            return false;
+        *v = {VF_MARCH_Y, f.shade ? (int)TAG_F32HY : (int)TAG_F32Y, f.shade != 0, false, false,
+              f.shade != 0, true, 0, 0};
+        return true;
+    }
     if (f.mode == VR_MODE_MIP || f.mode == VR_MODE_ISO) {  // base layouts only: no alternative copy
         const int k = f.count ? 1 : f.mip_inflight;  // the counting kernels walk step by step
         if (base < 0 || (k != 1 && k != 2 && k != 4)) return false;
@@ -82,12 +97,16 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
 }
 
 // The instantiations the library carries: 92 march_kernel, 32 march_pair_kernel, 56 mip_kernel,
-// 56 iso_kernel.
+// 56 iso_kernel, 2 march_y_kernel.
 constexpr bool variant_built(const FrameVariant &v)
 {
     const bool alt = v.tag == TAG_F32ALT || v.tag == TAG_F32P || v.tag == TAG_F32S;
     const bool field_type = v.tag == TAG_F32 || v.tag == TAG_F32H;
     if (v.tag < 0 || v.tag >= kVariantTags) return false;
+    if (v.family == VF_MARCH_Y)
+        return v.tag == (v.shade ? TAG_F32HY : TAG_F32Y) && v.gf == v.shade && v.pipe && !v.count &&
+               !v.skip;
+    if (v.tag == TAG_F32Y || v.tag == TAG_F32HY) return false;
     if (v.gf ? !(v.shade && field_type) : v.tag == TAG_F32H) return false;  // F32H: gf only
     switch (v.family) {
         case VF_MARCH: return !(v.pipe && (v.count || v.skip)) && !(alt && (v.count || v.skip));
@@ -99,13 +118,15 @@ constexpr bool variant_built(const FrameVariant &v)
 }
 
 // A dense numbering of every (family, tag, flags) combination, built or not: launch_frame's
-// table index and the variant part of the tile-schedule key.  5 flag bits: march shade, count,
-// skip, gf, pipe; pair shade, gf, 4 lanes; mip and iso count, skip, log2(inflight) (2 bits).
-constexpr int kVariantSlots = 4 * kVariantTags * 32;
+// table index and the variant part of the tile-schedule key.  5 flag bits: march and march_y
+// shade, count, skip, gf, pipe; pair shade, gf, 4 lanes; mip and iso count, skip, log2(inflight)
+// (2 bits).
+constexpr int kVariantSlots = kVariantFamilies * kVariantTags * 32;
 constexpr int variant_index(const FrameVariant &v)
 {
     const int k = v.inflight == 1 ? 0 : v.inflight == 2 ? 1 : v.inflight == 4 ? 2 : 3;
-    const int bits = v.family == VF_MARCH  ? v.shade << 4 | v.count << 3 | v.skip << 2 | v.gf << 1 | (int)v.pipe
+    const bool march = v.family == VF_MARCH || v.family == VF_MARCH_Y;
+    const int bits = march                 ? v.shade << 4 | v.count << 3 | v.skip << 2 | v.gf << 1 | (int)v.pipe
                      : v.family == VF_PAIR ? v.shade << 2 | v.gf << 1 | (v.lanes == 4)
                                            : v.count << 3 | v.skip << 2 | k;
     return (v.family * kVariantTags + v.tag) * 32 + bits;
@@ -115,7 +136,8 @@ constexpr FrameVariant variant_at(int i)
 {
     const int family = i / 32 / kVariantTags, tag = i / 32 % kVariantTags;
     const auto bit = [i](int b) { return (i >> b & 1) != 0; };
-    if (family == VF_MARCH) return {family, tag, bit(4), bit(3), bit(2), bit(1), bit(0), 0, 0};
+    if (family == VF_MARCH || family == VF_MARCH_Y)
+        return {family, tag, bit(4), bit(3), bit(2), bit(1), bit(0), 0, 0};
     if (family == VF_PAIR) return {family, tag, bit(2), false, false, bit(1), false, bit(0) ? 4 : 2, 0};
     return {family, tag, false, bit(3), bit(2), false, false, 0, (i & 3) == 3 ? 0 : 1 << (i & 3)};
 }
@@ -129,6 +151,8 @@ inline std::string variant_kernel_name(const FrameVariant &v)
     if (v.family == VF_MARCH)
         return ns + "march_kernel<" + vt + b(v.shade) + b(v.count) + b(v.skip) + b(v.gf) +
                b(v.pipe) + ">(vr::MarchParams)";
+    if (v.family == VF_MARCH_Y)
+        return ns + "march_y_kernel<" + vt + b(v.shade) + ">(vr::MarchParams)";
     if (v.family == VF_PAIR)
         return ns + "march_pair_kernel<" + vt + b(v.shade) + b(v.gf) + ", " +
                std::to_string(v.lanes) + ">(vr::MarchParams)";

@@ -76,7 +76,8 @@ class vr_dist_host_profile(C.Structure):  # vr_dist.h
 
 
 # vr.h enum vr_derived (vr_memory_info.last_downgrade)
-DERIVED = {1: "field", 2: "oblique_copy", 3: "plain_copy", 4: "stencil_copy", 5: "skip"}
+DERIVED = {1: "field", 2: "oblique_copy", 3: "plain_copy", 4: "stencil_copy", 5: "skip",
+           6: "ymajor_copy"}
 
 
 class vr_member_timing(C.Structure):  # vr_debug.h (ABI 7)
@@ -127,7 +128,8 @@ DIST_ID_BYTES = 128  # include/vr/vr_dist.h VR_DIST_ID_BYTES
 DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_member",
                  "vr_debug_create_members", "vr_debug_fail_member",
                  "vr_debug_host_profile_enable", "vr_debug_host_profile_member",
-                 "vr_debug_variant_name", "vr_debug_last_kernel_name"]
+                 "vr_debug_variant_name", "vr_debug_last_kernel_name",
+                 "vr_debug_ymajor_copy_bytes"]
 # include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
 MODE_COMPOSITE, MODE_MIP = 0, 1
@@ -228,6 +230,7 @@ def lib() -> C.CDLL:
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
         "vr_debug_last_kernel_name": (C.c_char_p, [vp]),
+        "vr_debug_ymajor_copy_bytes": (C.c_uint64, [vp]),
         "vr_cam_init": (None, [C.POINTER(vr_orbit_camera)]),
         "vr_cam_rotate": (None, [C.POINTER(vr_orbit_camera), f32, f32]),
         "vr_cam_zoom": (None, [C.POINTER(vr_orbit_camera), f32]),
@@ -641,7 +644,10 @@ class OffscreenPass:
     def memory_report(self) -> dict:
         m = vr_memory_info()
         self._check(lib().vr_memory_report(self._ctx, C.byref(m)), "memory_report")
-        return {n: int(getattr(m, n)) for n, _ in vr_memory_info._fields_}
+        r = {n: int(getattr(m, n)) for n, _ in vr_memory_info._fields_}
+        # the y-major copy has no field of its own in the ABI 9 struct (vr_debug.h)
+        r["ymajor_copy_bytes"] = int(lib().vr_debug_ymajor_copy_bytes(self._ctx))
+        return r
 
     def prepare(self, camera, params):
         cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
@@ -815,17 +821,17 @@ def code_object_symbols(path: Optional[str] = None):
 
 def kernel_code_hash(path: Optional[str] = None) -> str:
     """sha256 (16 hex digits) of the frame kernels' machine code in the library: every
-    instantiation of march_kernel, march_pair_kernel (lane groups: small row shares) and
-    order_tiles_kernel (the adaptive tile order inside a frame) -- gfx950 code bytes and kernel
-    descriptor (code_object_symbols).
+    instantiation of march_kernel, march_y_kernel (the y-major copy: the headline's view),
+    march_pair_kernel (lane groups: small row shares) and order_tiles_kernel (the adaptive tile
+    order inside a frame) -- gfx950 code bytes and kernel descriptor (code_object_symbols).
     Keys measured per-kernel figures (the PMC traffic bench.py's roofline reads) to the machine
     code they were measured on: host-only edits and changes to other kernels leave it
     unchanged, any change to a kernel a frame launches moves it (the build is deterministic;
     ADVICE r5: the pair and tile-order kernels were not hashed before)."""
     import hashlib
     syms = [(name, code) for name, code in code_object_symbols(path)
-            if any(k in name for k in (b"12march_kernel", b"17march_pair_kernel",
-                                       b"18order_tiles_kernel"))]
+            if any(k in name for k in (b"12march_kernel", b"14march_y_kernel",
+                                       b"17march_pair_kernel", b"18order_tiles_kernel"))]
     if not syms:
         raise RuntimeError(f"{path or LIB_PATH}: no march_kernel code in the gfx950 code object")
     h = hashlib.sha256()
