@@ -1098,6 +1098,108 @@ __device__ __forceinline__ void shade_sample(const MarchParams &P, const char *_
     phong(P, gx, gy_, gz, d0, d1, d2, s);
 }
 
+// ---- what the frame kernels share: a lane's pixel, the pixel's epilogue, the tile's frame ------
+// (The ray walk itself -- position update, bounds break, slab test -- stays spelled out in each
+// of march_strip, mip_strip, iso_strip and march_pair_kernel: every shared form of it tried
+// moved the composite kernels' machine code or the range kernels' registers; CHANGELOG.)
+
+// Row ly of this rank's share of the frame -> the frame's row gy (vr_internal.h RowShare);
+// false: below the frame.
+__device__ __forceinline__ bool share_row(const MarchParams &P, uint32_t ly, uint32_t &gy)
+{
+    const uint32_t blk = ly / P.row_block;
+    gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) * P.row_block +
+         (ly - blk * P.row_block);
+    return gy < P.H;
+}
+
+// The pixel of a lane: column px, row ly of the share (the output's row), gy of the frame.
+struct LanePixel {
+    uint32_t px, ly, gy;
+    bool active;  // inside the share and the frame
+};
+// Strip kernels: wavefront `wave` of the 16 x kMarchRows tile (tile_x, tile_y) covers ww x wh
+// pixels, ww = 2^wave_w_shift; the wavefronts together tile the tile.
+__device__ __forceinline__ LanePixel strip_pixel(const MarchParams &P, uint32_t tile_x,
+                                                 uint32_t tile_y, uint32_t wave, uint32_t lane)
+{
+    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
+    const uint32_t wpr = kTile >> ws;  // wavefronts per tile row
+    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
+    LanePixel pix;
+    pix.px = tile_x * kTile + (wave % wpr) * ww + lx_;
+    pix.ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
+    pix.active = pix.px < P.W && pix.ly < P.local_rows;
+    const bool in_frame = share_row(P, pix.ly, pix.gy);
+    pix.active = pix.active && in_frame;
+    return pix;
+}
+
+// The counting kernels' totals into vr_stats: rays, samples, shaded, steps, skipped.
+__device__ __forceinline__ void flush_counters(const MarchParams &P, uint32_t lane, bool covered,
+                                               unsigned long long n_samples,
+                                               unsigned long long n_shaded,
+                                               unsigned long long n_steps,
+                                               unsigned long long n_skipped)
+{
+    const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
+    const unsigned long long sm = wave_sum(n_samples);
+    const unsigned long long sh = wave_sum(n_shaded);
+    const unsigned long long st = wave_sum(n_steps);
+    const unsigned long long sk = wave_sum(n_skipped);
+    if (lane == 0) {
+        atomicAdd(&P.counters[0], rays);
+        atomicAdd(&P.counters[1], sm);
+        atomicAdd(&P.counters[2], sh);
+        atomicAdd(&P.counters[3], st);
+        atomicAdd(&P.counters[4], sk);
+    }
+}
+
+// volume.frag:50 + blend (offscreen_pass.cpp:715-725) of a ray's colour C and transmittance T
+// over the clear colour; an uncovered pixel has T = 1, C = 0 -> clear.
+__device__ __forceinline__ float4 blend_over_clear(const MarchParams &P, float cr, float cg,
+                                                   float cb, float T)
+{
+    const float A = 1.0f - T;
+    const float omA = 1.0f - A;
+    return make_float4(cr * A + P.clear[0] * omA, cg * A + P.clear[1] * omA,
+                       cb * A + P.clear[2] * omA, A * A + P.clear[3] * omA);
+}
+
+// The pixel's colour into the rank's output: RGBA8 (UNORM8 store :293) or RGBA32F.
+__device__ __forceinline__ void store_pixel(const MarchParams &P, uint32_t px, uint32_t ly,
+                                            float4 o)
+{
+    const size_t idx = (size_t)ly * P.W + px;
+    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
+    if (P.out_format == 0) {
+        static_cast<uint32_t *>(P.out)[idx] =
+            unorm8(o.x) | (unorm8(o.y) << 8) | (unorm8(o.z) << 16) | (unorm8(o.w) << 24);
+    } else {
+        static_cast<float4 *>(P.out)[idx] = o;
+    }
+}
+
+// The TF into LDS ({texel, difference to the next} pairs + sentinels) by the workgroup's
+// `threads` threads.
+__device__ __forceinline__ void stage_tf(const MarchParams &P, float4 *s_tf, int threads)
+{
+    for (int i = threadIdx.x; i < 2 * (P.tf_n + 2); i += threads) s_tf[i] = P.tf[i];
+}
+
+// Adaptive order: this tile's duration for the next launch (the workgroup's last step).
+__device__ __forceinline__ void write_tile_cost(const MarchParams &P, uint32_t tile_x,
+                                                uint32_t tile_y, long long wg_start)
+{
+    if (P.tile_cost) {
+        __syncthreads();
+        if (threadIdx.x == 0)
+            P.tile_cost[tile_y * P.tiles_x + tile_x] =
+                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
+    }
+}
+
 // PIPE: the loads of sample k + 1 are issued before sample k is filtered, shaded and
 // composited (two samples of the ray in flight).  For launches with few waves per CU (one
 // rank's share of a multi-GPU frame), where every wave's serial chain of memory round trips,
@@ -1114,20 +1216,10 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
     const long by_stride = (long)P.nbx * G::Elems;  // elements between brick rows/slabs
     const long bz_stride = (long)P.nbx * P.nby * G::Elems;
 
-    // wavefront -> (ww x wh) pixels, ww = 2^wave_w_shift, together tiling the 16 x kMarchRows tile
-    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
-    const uint32_t wpr = kTile >> ws;  // wavefronts per tile row
-    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
-    const uint32_t px = tile_x * kTile + (wave % wpr) * ww + lx_;
-    const uint32_t ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
-    bool active = px < P.W && ly < P.local_rows;
-    const uint32_t blk = ly / P.row_block;
-    const uint32_t gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) *
-                            P.row_block + (ly - blk * P.row_block);
-    active = active && gy < P.H;
+    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
 
     float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
-    const bool covered = active && pixel_ray(P, px, gy, tex, dir);
+    const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
 
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
     unsigned long long n_samples = 0, n_shaded = 0, n_steps = 0, n_skipped = 0;
@@ -1368,64 +1460,39 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
         p2 = p2 + d2 * P.step;
     }
 
-    if (COUNT) {
-        const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
-        const unsigned long long sm = wave_sum(n_samples);
-        const unsigned long long sh = wave_sum(n_shaded);
-        const unsigned long long st = wave_sum(n_steps);
-        const unsigned long long sk = wave_sum(n_skipped);
-        if (lane == 0) {
-            atomicAdd(&P.counters[0], rays);
-            atomicAdd(&P.counters[1], sm);
-            atomicAdd(&P.counters[2], sh);
-            atomicAdd(&P.counters[3], st);
-            atomicAdd(&P.counters[4], sk);
-        }
-    }
-    if (!active) return;
+    if (COUNT) flush_counters(P, lane, covered, n_samples, n_shaded, n_steps, n_skipped);
+    if (!pix.active) return;
 
-    // volume.frag:50 + blend (offscreen_pass.cpp:715-725); uncovered: T = 1, C = 0 -> clear
-    const float A = 1.0f - T;
-    const float omA = 1.0f - A;
-    const float o0 = cr * A + P.clear[0] * omA;
-    const float o1 = cg * A + P.clear[1] * omA;
-    const float o2 = cb * A + P.clear[2] * omA;
-    const float o3 = A * A + P.clear[3] * omA;
-    const size_t idx = (size_t)ly * P.W + px;
-    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
-    if (P.out_format == 0) {
-        static_cast<uint32_t *>(P.out)[idx] =
-            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
-    } else {
-        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
-    }
+    store_pixel(P, pix.px, pix.ly, blend_over_clear(P, cr, cg, cb, T));
+}
+
+// One workgroup's tile of a composite frame, the body of march_kernel and march_y_kernel: the
+// TF staged in LDS (when it fits), each wavefront its strip, the tile's duration written back.
+template <typename VT, bool SHADE, bool COUNT, bool SKIP, bool GF, bool PIPE>
+__device__ __forceinline__ void march_tile(const MarchParams &P, float4 *s_tf, uint32_t tile_x,
+                                           uint32_t tile_y, long long wg_start)
+{
+    const int tid = threadIdx.x;
+    const bool tf_in_lds = P.tf_n <= kTfLds;  // (always with PIPE: the host grants it no other TF)
+    if (tf_in_lds) stage_tf(P, s_tf, (int)kThreadsPerTile);
+    __syncthreads();
+    march_strip<VT, SHADE, COUNT, SKIP, GF, PIPE>(P, (LdsF4 *)s_tf, tf_in_lds, tile_x, tile_y,
+                                                  (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    write_tile_cost(P, tile_x, tile_y, wg_start);
 }
 
 template <typename VT, bool SHADE, bool COUNT, bool SKIP, bool GF, bool PIPE>
 __global__ __launch_bounds__(kThreadsPerTile, (kMarchMinWaves<COUNT, SKIP, GF, PIPE>)) void march_kernel(const MarchParams P)
 {
     __shared__ float4 s_tf[kTfLut];  // {texel, difference to the next} pairs + sentinels
-    const int tid = threadIdx.x;
-
     uint32_t tile_x, tile_y;
     if (!block_tile(P, tile_x, tile_y)) return;
     const long long wg_start = wall_clock64();
-
-    const bool tf_in_lds = P.tf_n <= kTfLds;
-    if (tf_in_lds)
-        for (int i = tid; i < 2 * (P.tf_n + 2); i += (int)kThreadsPerTile) s_tf[i] = P.tf[i];
-    __syncthreads();
-    march_strip<VT, SHADE, COUNT, SKIP, GF, PIPE>(P, (LdsF4 *)s_tf, tf_in_lds, tile_x, tile_y,
-                                                  (uint32_t)tid >> 6, (uint32_t)tid & 63u);
-    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
-        __syncthreads();
-        if (tid == 0)
-            P.tile_cost[tile_y * P.tiles_x + tile_x] =
-                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
-    }
+    march_tile<VT, SHADE, COUNT, SKIP, GF, PIPE>(P, s_tf, tile_x, tile_y, wg_start);
 #ifdef VR_WG_TIMES
     __syncthreads();
-    if (tid == 0) wg_times_record((unsigned long long)wg_start, tile_y * P.tiles_x + tile_x);
+    if (threadIdx.x == 0)
+        wg_times_record((unsigned long long)wg_start, tile_y * P.tiles_x + tile_x);
 #endif
 }
 
@@ -1440,24 +1507,9 @@ __global__ __launch_bounds__(kThreadsPerTile, (SHADE ? 6 : kMarchMinWaves<false,
 {
     static_assert(kYMajor<VT> && kHalfField<VT> == SHADE, "F32Y unshaded, F32HY shaded");
     __shared__ float4 s_tf[kTfLut];  // as march_kernel's
-    const int tid = threadIdx.x;
-
     uint32_t tile_x, tile_y;
     if (!block_tile(P, tile_x, tile_y)) return;
-    const long long wg_start = wall_clock64();
-
-    const bool tf_in_lds = P.tf_n <= kTfLds;  // (always: the host grants PIPE no other TF)
-    if (tf_in_lds)
-        for (int i = tid; i < 2 * (P.tf_n + 2); i += (int)kThreadsPerTile) s_tf[i] = P.tf[i];
-    __syncthreads();
-    march_strip<VT, SHADE, false, false, SHADE, true>(P, (LdsF4 *)s_tf, tf_in_lds, tile_x, tile_y,
-                                                      (uint32_t)tid >> 6, (uint32_t)tid & 63u);
-    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
-        __syncthreads();
-        if (tid == 0)
-            P.tile_cost[tile_y * P.tiles_x + tile_x] =
-                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
-    }
+    march_tile<VT, SHADE, false, false, SHADE, true>(P, s_tf, tile_x, tile_y, wall_clock64());
 }
 
 // ---- maximum-intensity projection (include/vr/vr_modes.h) ------------------------------------
@@ -1520,19 +1572,10 @@ __device__ __forceinline__ void mip_strip(const MarchParams &P, const MipArgs &M
                                           uint32_t tile_y, uint32_t wave, uint32_t lane)
 {
     using G = GeomOf<VT>;
-    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
-    const uint32_t wpr = kTile >> ws;
-    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
-    const uint32_t px = tile_x * kTile + (wave % wpr) * ww + lx_;
-    const uint32_t ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
-    bool active = px < P.W && ly < P.local_rows;
-    const uint32_t blk = ly / P.row_block;
-    const uint32_t gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) *
-                            P.row_block + (ly - blk * P.row_block);
-    active = active && gy < P.H;
+    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
 
     float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
-    const bool covered = active && pixel_ray(P, px, gy, tex, dir);
+    const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
 
     float m = -INFINITY;
     bool any = false;
@@ -1618,19 +1661,8 @@ __device__ __forceinline__ void mip_strip(const MarchParams &P, const MipArgs &M
         if (!COUNT && m >= end_at) live = false;
     }
 
-    if (COUNT) {
-        const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
-        const unsigned long long sm = wave_sum(n_samples);
-        const unsigned long long st = wave_sum(n_steps);
-        const unsigned long long sk = wave_sum(n_skipped);
-        if (lane == 0) {
-            atomicAdd(&P.counters[0], rays);
-            atomicAdd(&P.counters[1], sm);
-            atomicAdd(&P.counters[3], st);
-            atomicAdd(&P.counters[4], sk);
-        }
-    }
-    if (!active) return;
+    if (COUNT) flush_counters(P, lane, covered, n_samples, 0, n_steps, n_skipped);
+    if (!pix.active) return;
 
     // one composite step from T = 1 (volume.frag:42-45), then the blend over the clear colour
     float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
@@ -1642,20 +1674,7 @@ __device__ __forceinline__ void mip_strip(const MarchParams &P, const MipArgs &M
         cb = (s.z * s.w) * 1.0f;
         T = 1.0f * (1.0f - s.w);
     }
-    const float A = 1.0f - T;
-    const float omA = 1.0f - A;
-    const float o0 = cr * A + P.clear[0] * omA;
-    const float o1 = cg * A + P.clear[1] * omA;
-    const float o2 = cb * A + P.clear[2] * omA;
-    const float o3 = A * A + P.clear[3] * omA;
-    const size_t idx = (size_t)ly * P.W + px;
-    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
-    if (P.out_format == 0) {
-        static_cast<uint32_t *>(P.out)[idx] =
-            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
-    } else {
-        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
-    }
+    store_pixel(P, pix.px, pix.ly, blend_over_clear(P, cr, cg, cb, T));
 }
 
 template <typename VT, bool COUNT, bool SKIP, int K>
@@ -1666,12 +1685,7 @@ __global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams 
     if (!block_tile(P, tile_x, tile_y)) return;
     const long long wg_start = wall_clock64();
     mip_strip<VT, COUNT, SKIP, K>(P, M, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
-    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
-        __syncthreads();
-        if (tid == 0)
-            P.tile_cost[tile_y * P.tiles_x + tile_x] =
-                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
-    }
+    write_tile_cost(P, tile_x, tile_y, wg_start);
 }
 
 // ---- first-hit isosurface (include/vr/vr_iso.h) ----------------------------------------------
@@ -1702,19 +1716,10 @@ __device__ __forceinline__ void iso_strip(const MarchParams &P, const IsoArgs &I
     using G = GeomOf<VT>;
     const long by_stride = (long)P.nbx * G::Elems;  // elements between brick rows/slabs
     const long bz_stride = (long)P.nbx * P.nby * G::Elems;
-    const uint32_t ws = P.wave_w_shift, ww = 1u << ws, wh = 64u >> ws;
-    const uint32_t wpr = kTile >> ws;
-    const uint32_t lx_ = lane & (ww - 1), ly_ = lane >> ws;
-    const uint32_t px = tile_x * kTile + (wave % wpr) * ww + lx_;
-    const uint32_t ly = tile_y * kMarchRows + (wave / wpr) * wh + ly_;
-    bool active = px < P.W && ly < P.local_rows;
-    const uint32_t blk = ly / P.row_block;
-    const uint32_t gy = share_global_block(blk, P.rank, P.nranks, RowShare{P.share_w0, P.share_w}) *
-                            P.row_block + (ly - blk * P.row_block);
-    active = active && gy < P.H;
+    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
 
     float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
-    const bool covered = active && pixel_ray(P, px, gy, tex, dir);
+    const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
 
     const float iso = I.iso;
     bool hit = false, prev = false;
@@ -1822,21 +1827,9 @@ __device__ __forceinline__ void iso_strip(const MarchParams &P, const IsoArgs &I
     }
 
     const bool shade = hit && I.shading != 0;
-    if (COUNT) {
-        const unsigned long long rays = wave_sum(covered ? 1ull : 0ull);
-        const unsigned long long sm = wave_sum(n_samples);
-        const unsigned long long sh = wave_sum(shade ? 1ull : 0ull);
-        const unsigned long long st = wave_sum(n_steps);
-        const unsigned long long sk = wave_sum(n_skipped);
-        if (lane == 0) {
-            atomicAdd(&P.counters[0], rays);
-            atomicAdd(&P.counters[1], sm);
-            atomicAdd(&P.counters[2], sh);
-            atomicAdd(&P.counters[3], st);
-            atomicAdd(&P.counters[4], sk);
-        }
-    }
-    if (!active) return;
+    if (COUNT)
+        flush_counters(P, lane, covered, n_samples, shade ? 1ull : 0ull, n_steps, n_skipped);
+    if (!pix.active) return;
 
     // no hit: the clear colour, with an uncovered pixel's arithmetic (T = 1, C = 0)
     float o0 = 0.0f * 0.0f + P.clear[0] * 1.0f, o1 = 0.0f * 0.0f + P.clear[1] * 1.0f,
@@ -1889,14 +1882,7 @@ __device__ __forceinline__ void iso_strip(const MarchParams &P, const IsoArgs &I
         o2 = s.z;
         o3 = 1.0f;
     }
-    const size_t idx = (size_t)ly * P.W + px;
-    if (VR_OOB(4, idx * (P.out_format == 0 ? 4 : 16), P.out_bytes)) return;
-    if (P.out_format == 0) {
-        static_cast<uint32_t *>(P.out)[idx] =
-            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
-    } else {
-        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
-    }
+    store_pixel(P, pix.px, pix.ly, make_float4(o0, o1, o2, o3));
 }
 
 template <typename VT, bool COUNT, bool SKIP, int K>
@@ -1907,12 +1893,7 @@ __global__ __launch_bounds__(kThreadsPerTile) void iso_kernel(const MarchParams 
     if (!block_tile(P, tile_x, tile_y)) return;
     const long long wg_start = wall_clock64();
     iso_strip<VT, COUNT, SKIP, K>(P, I, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
-    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
-        __syncthreads();
-        if (tid == 0)
-            P.tile_cost[tile_y * P.tiles_x + tile_x] =
-                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
-    }
+    write_tile_cost(P, tile_x, tile_y, wg_start);
 }
 
 // ---- lane-pair march (small launches) ----------------------------------------------------------
@@ -1930,7 +1911,7 @@ __global__ __launch_bounds__(kThreads) void march_pair_kernel(const MarchParams 
     const int tid = threadIdx.x;
     uint32_t tile_x, tile_y;
     if (!block_tile(P, tile_x, tile_y)) return;
-    for (int i = tid; i < 2 * (P.tf_n + 2); i += kThreads) s_tf[i] = P.tf[i];
+    stage_tf(P, s_tf, kThreads);  // (no tf_in_lds test: the host grants these kernels no other TF)
     __syncthreads();
     const long long wg_start = wall_clock64();
 #ifdef VR_WG_TIMES
@@ -1940,7 +1921,9 @@ __global__ __launch_bounds__(kThreads) void march_pair_kernel(const MarchParams 
     const long by_stride = (long)P.nbx * G::Elems;
     const long bz_stride = (long)P.nbx * P.nby * G::Elems;
 
-    // L lanes per ray; wavefront = 16 x (4 / L) pixels; workgroup tile 16 x (16 / L)
+    // L lanes per ray; wavefront = 16 x (4 / L) pixels; workgroup tile 16 x (16 / L).  The row
+    // mapping is share_row's, spelled out: calling it here moves this kernel's machine code, which
+    // keys the committed traffic figures (vr_amd.kernel_code_hash; CHANGELOG, "Share the pixel")
     const uint32_t wave = tid >> 6, lane = tid & 63, q = lane / L, half = lane % L;
     const uint32_t px = tile_x * kTile + (q & 15);
     const uint32_t ly = tile_y * (kTile / L) + wave * (4 / L) + (q >> 4);
@@ -2031,30 +2014,13 @@ __global__ __launch_bounds__(kThreads) void march_pair_kernel(const MarchParams 
         prep(S0, k);
         if (consume(S1)) break;
     }
-    if (P.tile_cost) {  // adaptive order: this tile's duration for the next launch
-        __syncthreads();
-        if (tid == 0)
-            P.tile_cost[tile_y * P.tiles_x + tile_x] =
-                (uint32_t)min(wall_clock64() - wg_start, 0x7FFFFFFFLL);
-    }
+    write_tile_cost(P, tile_x, tile_y, wg_start);
 #ifdef VR_WG_TIMES
     __syncthreads();
     if (tid == 0) wg_times_record((unsigned long long)wg_t0, tile_y * P.tiles_x + tile_x);
 #endif
     if (!active || half) return;
-    const float A = 1.0f - T;  // volume.frag:50 + blend (offscreen_pass.cpp:715-725)
-    const float omA = 1.0f - A;
-    const float o0 = cr * A + P.clear[0] * omA;
-    const float o1 = cg * A + P.clear[1] * omA;
-    const float o2 = cb * A + P.clear[2] * omA;
-    const float o3 = A * A + P.clear[3] * omA;
-    const size_t idx = (size_t)ly * P.W + px;
-    if (P.out_format == 0) {
-        static_cast<uint32_t *>(P.out)[idx] =
-            unorm8(o0) | (unorm8(o1) << 8) | (unorm8(o2) << 16) | (unorm8(o3) << 24);
-    } else {
-        static_cast<float4 *>(P.out)[idx] = make_float4(o0, o1, o2, o3);
-    }
+    store_pixel(P, px, ly, blend_over_clear(P, cr, cg, cb, T));
 }
 
 // ---- adaptive tile order --------------------------------------------------------------------
