@@ -227,7 +227,8 @@ class BasicOffscreenPass {
     }
 
     // Extension (vr_modes.h): VR_MODE_COMPOSITE, the reference's composite, VR_MODE_MIP,
-    // maximum-intensity projection, or VR_MODE_ISO, the first-hit isosurface, for the frames
+    // maximum-intensity projection, VR_MODE_ISO, the first-hit isosurface, or VR_MODE_MINIP /
+    // VR_MODE_MEAN, the minimum- and mean-intensity projections, for the frames
     // recorded from now on (a UI toggle calls it like slicing_changed)
     void render_mode_changed(int mode) { check(vr_set_render_mode(ctx_, mode)); }
     int render_mode() const

@@ -2,7 +2,7 @@
  * vr_modes.h — render modes of a context (an addition beside vr.h; VR_ABI_VERSION and
  * vr_params are unchanged).
  *
- * A context renders in one of three modes.  The mode is context state, like the slice box: it
+ * A context renders in one of five modes.  The mode is context state, like the slice box: it
  * applies to every frame issued after the call, through vr_render, vr_render_device (row shares
  * included), vr_prepare, vr_count_work, vr_timing_*, vr_kernel_name and vr_dist_render.
  *
@@ -13,8 +13,13 @@
  *   VR_MODE_ISO        first-hit isosurface: the first point of the ray whose density reaches
  *                      the context's isovalue, drawn as a lit opaque surface (vr_iso.h has the
  *                      isovalue's entry points and the semantics).
+ *   VR_MODE_MINIP      minimum-intensity projection: the pixel shows the smallest density
+ *                      sample of its ray (the thin-slab view of airways and other low-density
+ *                      structures; meant to be used with the slice box, see below).
+ *   VR_MODE_MEAN       mean-intensity projection: the average of the ray's density samples,
+ *                      looked up in the transfer function once (the "X-ray" / thick-slab look).
  *
- * The value 2 is unassigned: vr_set_render_mode refuses it like any unknown mode.
+ * The values 2 and 5 are unassigned: vr_set_render_mode refuses them like any unknown mode.
  *
  * MIP semantics.  The ray is the composite's: the same pixel ray and entry point, nsteps =
  * int(ray_dist / step), the position update p = p + dir * step in f32, the bounds break and the
@@ -49,6 +54,39 @@
  *
  * MIP reads the volume's base bricks only: it builds and evicts no difference field and no
  * alternative copy.
+ *
+ * MinIP and mean semantics.  The ray, the filter, the epilogue, both output formats and the
+ * vr_params table are MIP's; what is kept along the ray differs.  Per covered pixel:
+ *
+ *     MinIP:  m = +INFINITY; any = false
+ *             each in-slab step:  d = trilinear(pos);  m = fminf(m, d);  any = true
+ *                                                      (a NaN sample leaves m unchanged)
+ *             v = m
+ *     Mean:   sum = 0.0f; n = 0
+ *             each in-slab step, in step order:  d = trilinear(pos);  sum = sum + d;  n = n + 1
+ *                                 (one f32 addition per sample, so the order is part of the
+ *                                 result; a NaN or infinite sample propagates as IEEE addition says)
+ *             any = n > 0;  v = sum / (float)n         the correctly rounded f32 quotient
+ *     both:   if !any: pixel = clear colour
+ *             else: t = (v - vmin) / (vmax - vmin);  s = tf(t)      (a NaN t reads texel 0)
+ *                   one composite step from T = 1, then the blend over the clear colour, as MIP
+ *
+ * Every kernel variant renders the same bytes: the minimum does not depend on the order, and the
+ * mean's additions are made in step order whatever the number of samples in flight.
+ *
+ *   skip_empty = 1   range skipping, same pixels, from the per-brick value ranges alone (as MIP:
+ *                    no transfer-function dependence, VR_DERIVED_SKIP downgrade over the budget).
+ *                    MinIP: a sample in a brick whose stored minimum is not below the ray's
+ *                    running minimum is not fetched.  Mean: a sample in a brick whose values are
+ *                    all one finite number c is not fetched and adds c (it still counts in n).
+ * vr_stats from vr_count_work: as MIP; samples + skipped_samples is the number of in-slab steps.
+ *
+ * One wart: the sampler is the composite's CLAMP_TO_BORDER, so a sample within half a voxel of a
+ * cube face blends with 0.  A MinIP over the whole cube is therefore dominated by its entry and
+ * exit samples: use MinIP with a slice box inset by at least half a voxel on every side.
+ *
+ * Like MIP, both read the base bricks only: no difference field, no alternative copy, nothing
+ * evicted.
  */
 #ifndef VR_VR_MODES_H
 #define VR_VR_MODES_H
@@ -59,7 +97,8 @@
 extern "C" {
 #endif
 
-enum vr_render_mode { VR_MODE_COMPOSITE = 0, VR_MODE_MIP = 1, VR_MODE_ISO = 3 /* 2: unassigned */ };
+enum vr_render_mode { VR_MODE_COMPOSITE = 0, VR_MODE_MIP = 1, VR_MODE_ISO = 3,
+                      VR_MODE_MINIP = 4, VR_MODE_MEAN = 6 /* 2, 5: unassigned */ };
 
 /* Set the mode of the frames issued from now on (frames already issued keep theirs; a
  * multi-device context forwards it to every device once its issued frames are done).

@@ -1167,10 +1167,45 @@ int iso_inflight(const vr_ctx *c, bool skip)
     if (c->layout & kQuadFlag) return 4;
     return skip ? 2 : 4;
 }
-// MIP and ISO frames read the base bricks through ensure_mip and launch with these facts
+// The same for proj_kernel (VR_MODE_MINIP and VR_MODE_MEAN; the knob forces both).  The loads and
+// their issue order are MIP's, and so are the choices, but for one, by measurement
+// (tools/proj_bench.py, profiles/r11/proj/; ms per frame, K = 1 / 2 / 4, MinIP then mean; "slab":
+// the central half of the cube along the view axis):
+//   8-bit yz-quads (C2): 2 without skipping (fill 0.301 / 0.264 / 0.273 and 0.290 / 0.259 /
+//     0.269, slab 0.315 / 0.276 / 0.279 and 0.304 / 0.272 / 0.276), 4 with (fill 0.310 / 0.270 /
+//     0.261 and 0.357 / 0.339 / 0.333);
+//   plain 8-bit bricks (C4): 2 (fill 1.192 / 1.039 / 1.034 and 1.162 / 1.016 / 1.019; with
+//     skipping 1.312 / 1.104 / 1.349 and 1.832 / 1.623 / 1.910);
+//   f32 (C3): MinIP 2 (fill 0.393 / 0.344 / 0.355, with skipping 0.409 / 0.365 / 0.422); the
+//     mean 4 without skipping (fill 0.392 / 0.344 / 0.339, slab 0.351 / 0.282 / 0.273: its
+//     consume half is one addition per sample) and 2 with (0.582 / 0.493 / 0.568); on sparse
+//     views (the default camera) as MIP, 1 without skipping (0.252 / 0.292 / 0.300 and 0.252 /
+//     0.292 / 0.295; with the slab K = 4 is ahead, 0.183 / 0.175 / 0.171, and is not chosen: the
+//     policy does not look at the slice box) and 4 with (0.231 / 0.195 / 0.178 and 0.298 / 0.272 /
+//     0.266);
+//   16-bit yz-quads: MIP's choice (not measured).
+int proj_inflight(const vr_ctx *c, bool skip)
+{
+    if (c->knobs.mip_inflight) return c->knobs.mip_inflight;
+    if (c->render_mode == VR_MODE_MEAN && c->layout == ST_F32 && !skip && c->pixel_span <= kAltSpan)
+        return 4;
+    return mip_inflight(c, skip);
+}
+bool proj_mode(const vr_ctx *c)
+{
+    return c->render_mode == VR_MODE_MINIP || c->render_mode == VR_MODE_MEAN;
+}
+int range_inflight(const vr_ctx *c, bool skip)
+{
+    return c->render_mode == VR_MODE_ISO ? iso_inflight(c, skip)
+           : proj_mode(c)                ? proj_inflight(c, skip)
+                                         : mip_inflight(c, skip);
+}
+// MIP, ISO, MinIP and mean frames read the base bricks through ensure_mip and launch with
+// these facts
 bool range_mode(const vr_ctx *c)
 {
-    return c->render_mode == VR_MODE_MIP || c->render_mode == VR_MODE_ISO;
+    return c->render_mode == VR_MODE_MIP || c->render_mode == VR_MODE_ISO || proj_mode(c);
 }
 IsoArgs iso_args(const vr_ctx *c, const vr_params *p, const MipArgs &M)
 {
@@ -1334,9 +1369,7 @@ VariantFacts launch_facts(const vr_ctx *c, const vr_params *p, const MarchParams
                           bool count)
 {
     const bool skip = P.skip_empty != 0;  // skip: granted
-    const int k = c->render_mode == VR_MODE_MIP   ? mip_inflight(c, skip)
-                  : c->render_mode == VR_MODE_ISO ? iso_inflight(c, skip)
-                                                  : 0;
+    const int k = range_mode(c) ? range_inflight(c, skip) : 0;
     return {layout, c->render_mode, p->shading != 0, count, skip, P.grad != nullptr, P.grad_half,
             P.pipelined, P.tf_n, P.pair, k};
 }
@@ -1357,7 +1390,7 @@ VariantFacts next_frame_facts(const vr_ctx *c, const vr_params *p)
     f.tf_n = (int32_t)c->tf_n;
     if (range_mode(c)) {
         f.skip = p && p->skip_empty && c->range_valid && c->nbricks_alloc;
-        f.mip_inflight = f.mode == VR_MODE_ISO ? iso_inflight(c, f.skip) : mip_inflight(c, f.skip);
+        f.mip_inflight = range_inflight(c, f.skip);
         return f;
     }
     f.skip = p && p->skip_empty;
@@ -2137,7 +2170,8 @@ int vr_set_slicing(vr_ctx *c, const float min_slice[3], const float max_slice[3]
 int vr_set_render_mode(vr_ctx *c, int mode)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP && mode != VR_MODE_ISO)  // 2: unassigned
+    if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP && mode != VR_MODE_ISO &&
+        mode != VR_MODE_MINIP && mode != VR_MODE_MEAN)  // 2, 5: unassigned
         return fail(c, VR_EINVAL, "unknown render mode");
     if (is_group(c)) {  // frames already issued keep the old mode (as the slice box)
         if (int rc = group_idle(c)) return rc;
@@ -2359,7 +2393,10 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
         HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
     }
     HIP_TRY(c, launch_frame(v, P, M, iso_args(c, p, M), s),
-            v.family == VF_ISO ? "iso kernel launch" : mip ? "mip kernel launch" : "march kernel launch");
+            v.family == VF_ISO    ? "iso kernel launch"
+            : v.family == VF_PROJ ? "proj kernel launch"
+            : mip                 ? "mip kernel launch"
+                                  : "march kernel launch");
     c->last_variant = v;
     if (timing) {
         HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
@@ -2571,7 +2608,10 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
     FrameVariant v;
     resolve_variant(launch_facts(c, p, P, c->layout, true), &v);
     HIP_TRY(c, launch_frame(v, P, M, iso_args(c, p, M), nullptr),
-            v.family == VF_ISO ? "iso (count) launch" : mip ? "mip (count) launch" : "march (count) launch");
+            v.family == VF_ISO    ? "iso (count) launch"
+            : v.family == VF_PROJ ? "proj (count) launch"
+            : mip                 ? "mip (count) launch"
+                                  : "march (count) launch");
     c->last_variant = v;
     unsigned long long h[5];
     HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");

@@ -457,9 +457,17 @@ struct IsoArgs {
     float iso;
     int32_t shading;
 };
-// The kernel `v` names (resolve_variant) over p's tiles; m is read by mip_kernel alone, i by
-// iso_kernel alone.  hipErrorInvalidValue: no such kernel (variant_built), or MIP / ISO
-// skipping without the brick ranges.
+// ---- Minimum- and mean-intensity projection (include/vr/vr_modes.h, proj_kernel) ----
+// What proj_kernel reads beside MarchParams (its own argument, as MipArgs): the brick ranges of
+// MipArgs, null without range skipping.  MinIP reads .x of the entry after the last brick, the
+// smallest lo of all.
+struct ProjArgs {
+    const float2 *brick_range;
+    uint32_t nbricks;
+};
+// The kernel `v` names (resolve_variant) over p's tiles; m is read by mip_kernel and (as its
+// ProjArgs) proj_kernel, i by iso_kernel alone.  hipErrorInvalidValue: no such kernel
+// (variant_built), or MIP / ISO / MinIP / mean skipping without the brick ranges.
 hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
                         const IsoArgs &i, hipStream_t stream);
 constexpr int kMipDefaultInFlight = 2;

@@ -1688,6 +1688,175 @@ __global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams 
     write_tile_cost(P, tile_x, tile_y, wg_start);
 }
 
+// ---- minimum- and mean-intensity projection (include/vr/vr_modes.h) --------------------------
+// mip_strip's ray and batch loop (K steps' loads issued before any is filtered; dead, off-slab
+// and skipped lanes load element 0; with SKIP a step no lane fetches issues no load), keeping
+// another quantity of the ray.  The pixel reads the TF once, at v, with MIP's epilogue.
+//
+// OP = kProjMin: v is the smallest sample, m = fminf(m, d) from +INFINITY.  fminf is exact and
+// commutative and ignores a NaN operand, so neither the order nor K shows in the frame.
+//   SKIP mirrors MIP's: a sample whose brick's stored minimum lo is not below the running
+//   minimum is not fetched.  8/16-bit voxels: b - a is exact, so each lerp level is the
+//   correctly rounded value of a point between a and b and cannot pass below min(a, b):
+//   tri >= lo.  f32: a level can pass min(a, b) by an ulp of the larger operand, so lo is
+//   lowered by the classifier's margin 4e-6 (|lo| + |hi|) (-INFINITY when b - a can overflow).
+//   !(lo >= m) keeps NaN bricks; m is read as it stood before the batch.  A ray of an 8/16-bit
+//   volume ends once m reaches the smallest lo of the volume (then a sample was taken: m is
+//   finite only after one).
+// OP = kProjMean: v = sum / (float)n, sum one f32 addition per in-slab sample from +0.  The
+// order of the additions is part of the result: the consume half of a batch adds its K samples
+// in step order into the one running sum, so every K gives the reference's bits.
+//   SKIP: a sample whose brick has lo == hi, finite, is not fetched and adds lo at its step's
+//   place (it counts in n).  Exact: every voxel the sample can read is c = lo, each lerp level
+//   is fmaf(w, c - c, c) = fmaf(w, 0, c) = c for finite c.  An infinite c gives inf - inf =
+//   NaN, so such a brick is fetched; a NaN brick stores (NaN, NaN) and lo == hi is false.  A
+//   brick of mixed +0 / -0 also has lo == hi and adds a zero of either sign where the filter
+//   gives one of either sign: x + (+-0) = x for x != 0, +0 + (+-0) = +0, and a sum that
+//   started at +0 is never -0 (two operands sum to -0 only when both are -0), so the sign
+//   never shows.  There is no early end.
+// COUNT: walks every step, fetches and skips per lane, and fills vr_stats (shaded 0); samples +
+// skipped is the number of in-slab steps.
+template <typename VT, int OP, bool COUNT, bool SKIP, int K>
+__device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs &M, uint32_t tile_x,
+                                           uint32_t tile_y, uint32_t wave, uint32_t lane)
+{
+    static_assert(OP == kProjMin || OP == kProjMean, "minimum or mean");
+    static_assert(!COUNT || K == 1, "the counting kernels walk one step at a time");
+    constexpr bool MEAN = OP == kProjMean;
+    using G = GeomOf<VT>;
+    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
+
+    float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
+    const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
+
+    float m = MEAN ? 0.0f : INFINITY;  // the running minimum, or the running sum
+    int n = 0;                         // mean: in-slab samples so far
+    bool any = false;
+    unsigned long long n_samples = 0, n_steps = 0, n_skipped = 0;
+    uint32_t cur_brick = 0xFFFFFFFFu;
+    float cur_lo = MEAN ? NAN : -INFINITY;  // min: the brick's (lowered) lo; mean: its constant or NaN
+    const char *__restrict__ vol = static_cast<const char *>(P.vol);
+    const int nsteps = covered ? P.nsteps : 0;
+    float p0 = tex[0], p1 = tex[1], p2 = tex[2];
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
+    float end_at = -INFINITY;  // 8/16-bit volumes: no sample is below the smallest brick minimum
+    if constexpr (!MEAN && SKIP && !COUNT && !kZPair<VT>) end_at = M.brick_range[M.nbricks].x;
+
+    struct Stage {
+        MipRaw<VT> r;
+        float ax, ay, az;
+        float c;  // mean with SKIP: what a sample that is not fetched adds
+        bool slab, fetch, issued;
+    };
+    bool live = nsteps > 0;
+    for (int it = 0; live; it += K) {
+        Stage S[K];
+        const float m_in = m;
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const int k = it + s;
+            const bool interior = (unsigned)(k - 1) < (unsigned)kin;
+            // volume.frag:34-37: the first position outside ends the ray
+            live = live && k < nsteps &&
+                   (interior || !(p0 > 1.0f || p1 > 1.0f || p2 > 1.0f || p0 < 0.0f || p1 < 0.0f ||
+                                  p2 < 0.0f));
+            if (COUNT && live) ++n_steps;
+            // volume.frag:39-40 (strict)
+            const bool slab = live && (interior || (p0 < P.smax[0] && p1 < P.smax[1] &&
+                                                    p2 < P.smax[2] && p0 > P.smin[0] &&
+                                                    p1 > P.smin[1] && p2 > P.smin[2]));
+            int i, j, kk;
+            texel_coord(p0, P.fnx, i, S[s].ax);
+            texel_coord(p1, P.fny, j, S[s].ay);
+            texel_coord(p2, P.fnz, kk, S[s].az);
+            const int pi = i + kPad, pj = j + kPad, pk = kk + kPad;
+            bool fetch = slab;
+            if constexpr (SKIP) {
+                if (slab) {
+                    const uint32_t bb = ((uint32_t)pk / G::BZ * P.nby + (uint32_t)pj / G::BY) * P.nbx +
+                                        (uint32_t)pi / G::BX;
+                    if (bb != cur_brick) {
+                        cur_brick = bb;
+                        const float2 r = VR_OOB(7, bb, M.nbricks) ? make_float2(NAN, NAN)
+                                                                   : M.brick_range[bb];
+                        if constexpr (MEAN)
+                            cur_lo = (r.x == r.y && fabsf(r.x) < INFINITY) ? r.x : NAN;
+                        else
+                            cur_lo = kZPair<VT> ? r.x - (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.x;
+                    }
+                    fetch = MEAN ? cur_lo != cur_lo : !(cur_lo >= m_in);
+                }
+                S[s].c = cur_lo;
+            }
+            if (COUNT && slab) {
+                if (fetch)
+                    ++n_samples;
+                else
+                    ++n_skipped;
+            }
+            any = any || slab;
+            S[s].slab = slab;
+            S[s].fetch = fetch;
+            size_t ce = fetch ? cell_offset<VT>(pi, pj, pk, P.nbx, P.nby) : (size_t)0;
+            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+            // without SKIP every step loads; with it a step no lane of the wave fetches does not
+            S[s].issued = !SKIP || __any(fetch);
+            if (S[s].issued) S[s].r.issue(vol, ce);
+            // volume.frag:47
+            p0 = p0 + d0 * P.step;
+            p1 = p1 + d1 * P.step;
+            p2 = p2 + d2 * P.step;
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {  // in step order: the mean's additions are ordered
+            float d = 0.0f;
+            if (S[s].issued) {
+                Cell8<VT> c;
+                S[s].r.decode(c);
+                d = c.tri(S[s].ax, S[s].ay, S[s].az);
+            }
+            if constexpr (MEAN) {
+                if constexpr (SKIP) d = S[s].fetch ? d : S[s].c;
+                if (S[s].slab) {
+                    m = m + d;
+                    ++n;
+                }
+            } else {
+                if (S[s].fetch) m = fminf(m, d);  // a NaN sample leaves m
+            }
+        }
+        if (!MEAN && !COUNT && m <= end_at) live = false;
+    }
+
+    if (COUNT) flush_counters(P, lane, covered, n_samples, 0, n_steps, n_skipped);
+    if (!pix.active) return;
+
+    // one composite step from T = 1 (volume.frag:42-45), then the blend over the clear colour
+    float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    if (any) {
+        const float v = MEAN ? m / (float)n : m;  // (the correctly rounded quotient: Makefile)
+        const float tt = div_by_range(v - P.vmin, P);
+        const float4 s = tf_lookup(P.tf, P.tf_n, P.tf_nf, tt);
+        cr = (s.x * s.w) * 1.0f;
+        cg = (s.y * s.w) * 1.0f;
+        cb = (s.z * s.w) * 1.0f;
+        T = 1.0f * (1.0f - s.w);
+    }
+    store_pixel(P, pix.px, pix.ly, blend_over_clear(P, cr, cg, cb, T));
+}
+
+template <typename VT, int OP, bool COUNT, bool SKIP, int K>
+__global__ __launch_bounds__(kThreadsPerTile) void proj_kernel(const MarchParams P, const ProjArgs M)
+{
+    const int tid = threadIdx.x;
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    const long long wg_start = wall_clock64();
+    proj_strip<VT, OP, COUNT, SKIP, K>(P, M, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    write_tile_cost(P, tile_x, tile_y, wg_start);
+}
+
 // ---- first-hit isosurface (include/vr/vr_iso.h) ----------------------------------------------
 // The same ray as march_strip and mip_strip, but the pixel shows the first in-slab sample whose
 // density reaches the isovalue: a search with an ordered early exit, then -- once the whole
@@ -2660,6 +2829,9 @@ void launch_slot(uint32_t nblocks, const MarchParams &p, const MipArgs &m, const
     else if constexpr (v.family == VF_MIP)
         hipLaunchKernelGGL((mip_kernel<VT, v.count, v.skip, v.inflight>), dim3(nblocks),
                            dim3(kThreadsPerTile), 0, stream, p, m);
+    else if constexpr (v.family == VF_PROJ)
+        hipLaunchKernelGGL((proj_kernel<VT, v.op, v.count, v.skip, v.inflight>), dim3(nblocks),
+                           dim3(kThreadsPerTile), 0, stream, p, ProjArgs{m.brick_range, m.nbricks});
     else
         hipLaunchKernelGGL((iso_kernel<VT, v.count, v.skip, v.inflight>), dim3(nblocks),
                            dim3(kThreadsPerTile), 0, stream, p, iso);
@@ -2742,7 +2914,7 @@ hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipAr
     static constexpr auto launchers = slot_launchers(std::make_integer_sequence<int, kVariantSlots>{});
     const int i = variant_index(v);
     const FrameLauncher fn = i >= 0 && i < kVariantSlots ? launchers[(size_t)i] : nullptr;
-    if (!fn || (v.family == VF_MIP && v.skip && !m.brick_range) ||
+    if (!fn || ((v.family == VF_MIP || v.family == VF_PROJ) && v.skip && !m.brick_range) ||
         (v.family == VF_ISO && v.skip && !iso.brick_range))
         return hipErrorInvalidValue;
     if (p.tiles_x * p.tiles_y == 0) return hipSuccess;

@@ -1,12 +1,12 @@
 // vr_variant.h — which kernel a launch runs, stated once.
 //
 // A frame (or a vr_count_work pass) runs one instantiation of march_kernel, march_pair_kernel,
-// mip_kernel, iso_kernel or march_y_kernel: a FrameVariant.  resolve_variant is the only place the mapping from
+// mip_kernel, iso_kernel, proj_kernel or march_y_kernel: a FrameVariant.  resolve_variant is the only place the mapping from
 // a launch's resolved inputs (VariantFacts) to it is written, variant_built the only list of the
 // instantiations the library carries; the launch (launch_frame, vr_kernels.hip), the name a
 // profiler reports and the tile-schedule key all derive from the one FrameVariant.  The policy
 // -- which facts a view gets -- is not here (use_pipeline, use_grad_field, use_pair, want_alt,
-// mip_inflight, iso_inflight in vr_api.hip).  Plain C++17, no HIP types.
+// mip_inflight, iso_inflight, proj_inflight in vr_api.hip).  Plain C++17, no HIP types.
 #pragma once
 
 #include <stdint.h>
@@ -25,8 +25,9 @@ constexpr int kQuadFlag = 0x10, kAltFlag = 0x20, kPlainF32Flag = 0x100, kStencil
               kYMajorFlag = 0x400;
 constexpr int kTfLds = 256;  // TF texels staged in LDS (lane groups and pipelining need it there)
 
-enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2, VF_ISO = 3, VF_MARCH_Y = 4 };
-constexpr int kVariantFamilies = 5;
+enum VariantFamily { VF_NONE = -1, VF_MARCH = 0, VF_PAIR = 1, VF_MIP = 2, VF_ISO = 3, VF_MARCH_Y = 4,
+                     VF_PROJ = 5 };
+constexpr int kVariantFamilies = 6;
 // The kernels' storage type tag (their first template argument): kTagNames and launch_frame's
 // type list follow this order.  TAG_F32H: the ST_F32 bricks read with the binary16 field.
 // TAG_F32Y / TAG_F32HY: the y-major copy (kYMajorFlag), unshaded / shaded with the binary16
@@ -41,15 +42,17 @@ constexpr const char *kTagNames[kVariantTags] = {
     "vr::F32S", "vr::F32Y", "vr::F32HY"};
 
 // march_kernel<VT, shade, count, skip, gf, pipe>, march_pair_kernel<VT, shade, gf, lanes>,
-// mip_kernel<VT, count, skip, inflight>, iso_kernel<VT, count, skip, inflight> or
-// march_y_kernel<VT, shade> (the pipelined single-lane march, gf = shade); what a family does
-// not take stays false / 0.
+// mip_kernel<VT, count, skip, inflight>, iso_kernel<VT, count, skip, inflight>,
+// proj_kernel<VT, op, count, skip, inflight> or march_y_kernel<VT, shade> (the pipelined
+// single-lane march, gf = shade); what a family does not take stays false / 0.
 struct FrameVariant {
     int family = VF_NONE, tag = 0;
     bool shade = false, count = false, skip = false, gf = false, pipe = false;
     int lanes = 0;     // lanes per ray: 2 or 4
     int inflight = 0;  // samples of a ray in flight: 1, 2 or 4
+    int op = 0;        // proj_kernel: kProjMin or kProjMean
 };
+constexpr int kProjMin = 0, kProjMean = 1;  // proj_kernel's OP (VR_MODE_MINIP, VR_MODE_MEAN)
 
 // The resolved inputs of the decision, after the derived structures a launch reads were built
 // or refused (the fields: vr_debug.h).
@@ -84,6 +87,13 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
               false, 0, k};
         return true;
     }
+    if (f.mode == VR_MODE_MINIP || f.mode == VR_MODE_MEAN) {  // base layouts only, as MIP
+        const int k = f.count ? 1 : f.mip_inflight;
+        if (base < 0 || (k != 1 && k != 2 && k != 4)) return false;
+        *v = {VF_PROJ, base, false, f.count != 0, f.skip != 0, false, false, 0, k,
+              f.mode == VR_MODE_MEAN ? kProjMean : kProjMin};
+        return true;
+    }
     // an alternative copy carries no skip-empty structures, field or lane groups, and no counts
     if (base < 0 && (alt < 0 || f.count || f.pair || f.skip || f.field)) return false;
     const bool gf = base == TAG_F32 && f.shade && f.field;  // shaded f32 launches read the field
@@ -97,7 +107,7 @@ inline bool resolve_variant(const VariantFacts &f, FrameVariant *v)
 }
 
 // The instantiations the library carries: 92 march_kernel, 32 march_pair_kernel, 56 mip_kernel,
-// 56 iso_kernel, 2 march_y_kernel.
+// 56 iso_kernel, 2 march_y_kernel, 112 proj_kernel.
 constexpr bool variant_built(const FrameVariant &v)
 {
     const bool alt = v.tag == TAG_F32ALT || v.tag == TAG_F32P || v.tag == TAG_F32S;
@@ -113,6 +123,9 @@ constexpr bool variant_built(const FrameVariant &v)
         case VF_PAIR: return !alt && (v.lanes == 2 || v.lanes == 4);
         case VF_MIP:
         case VF_ISO: return !alt && (v.inflight == 1 || (!v.count && (v.inflight == 2 || v.inflight == 4)));
+        case VF_PROJ:
+            return !alt && (v.op == kProjMin || v.op == kProjMean) &&
+                   (v.inflight == 1 || (!v.count && (v.inflight == 2 || v.inflight == 4)));
         default: return false;
     }
 }
@@ -120,7 +133,7 @@ constexpr bool variant_built(const FrameVariant &v)
 // A dense numbering of every (family, tag, flags) combination, built or not: launch_frame's
 // table index and the variant part of the tile-schedule key.  5 flag bits: march and march_y
 // shade, count, skip, gf, pipe; pair shade, gf, 4 lanes; mip and iso count, skip, log2(inflight)
-// (2 bits).
+// (2 bits); proj op, count, skip, log2(inflight).
 constexpr int kVariantSlots = kVariantFamilies * kVariantTags * 32;
 constexpr int variant_index(const FrameVariant &v)
 {
@@ -128,6 +141,7 @@ constexpr int variant_index(const FrameVariant &v)
     const bool march = v.family == VF_MARCH || v.family == VF_MARCH_Y;
     const int bits = march                 ? v.shade << 4 | v.count << 3 | v.skip << 2 | v.gf << 1 | (int)v.pipe
                      : v.family == VF_PAIR ? v.shade << 2 | v.gf << 1 | (v.lanes == 4)
+                     : v.family == VF_PROJ ? (v.op == kProjMean) << 4 | v.count << 3 | v.skip << 2 | k
                                            : v.count << 3 | v.skip << 2 | k;
     return (v.family * kVariantTags + v.tag) * 32 + bits;
 }
@@ -139,7 +153,8 @@ constexpr FrameVariant variant_at(int i)
     if (family == VF_MARCH || family == VF_MARCH_Y)
         return {family, tag, bit(4), bit(3), bit(2), bit(1), bit(0), 0, 0};
     if (family == VF_PAIR) return {family, tag, bit(2), false, false, bit(1), false, bit(0) ? 4 : 2, 0};
-    return {family, tag, false, bit(3), bit(2), false, false, 0, (i & 3) == 3 ? 0 : 1 << (i & 3)};
+    return {family, tag, false, bit(3), bit(2), false, false, 0, (i & 3) == 3 ? 0 : 1 << (i & 3),
+            family == VF_PROJ && bit(4) ? kProjMean : kProjMin};
 }
 
 // The demangled kernel name, as rocprofv3's kernel trace reports it ("Kernel_Name").
@@ -156,6 +171,9 @@ inline std::string variant_kernel_name(const FrameVariant &v)
     if (v.family == VF_PAIR)
         return ns + "march_pair_kernel<" + vt + b(v.shade) + b(v.gf) + ", " +
                std::to_string(v.lanes) + ">(vr::MarchParams)";
+    if (v.family == VF_PROJ)
+        return ns + "proj_kernel<" + vt + ", " + std::to_string(v.op) + b(v.count) + b(v.skip) + ", " +
+               std::to_string(v.inflight) + ">(vr::MarchParams, vr::ProjArgs)";
     return ns + (v.family == VF_ISO ? "iso_kernel<" : "mip_kernel<") + vt + b(v.count) + b(v.skip) +
            ", " + std::to_string(v.inflight) +
            (v.family == VF_ISO ? ">(vr::MarchParams, vr::IsoArgs)" : ">(vr::MarchParams, vr::MipArgs)");

@@ -9,7 +9,8 @@
 //   vr_cli <file.nhdr|file.nrrd|synthetic:N> <out.ppm> [--size WxH] [--radius R]
 //          [--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS]
 //          [--skip-empty] [--frames K] [--device-mask M]   (M: render every frame across these GPUs)
-//          [--mode composite|mip|iso]   (mip: maximum-intensity projection, include/vr/vr_modes.h;
+//          [--mode composite|mip|iso|minip|mean]   (mip / minip / mean: maximum-, minimum- and
+//                                        mean-intensity projection, include/vr/vr_modes.h;
 //                                        iso: first-hit isosurface, include/vr/vr_iso.h)
 //          [--iso V]   (the isosurface's density, in the volume's units; default 0)
 #include <chrono>
@@ -27,7 +28,7 @@ int main(int argc, char **argv)
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <file.nhdr|synthetic:N> <out.ppm> [--size WxH] [--radius R] "
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
-                             "[--frames K] [--device-mask M] [--mode composite|mip|iso] [--iso V]\n",
+                             "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V]\n",
                      argv[0]);
         return 2;
     }
@@ -56,7 +57,7 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (mode != "composite" && mode != "mip" && mode != "iso") {
+    if (mode != "composite" && mode != "mip" && mode != "iso" && mode != "minip" && mode != "mean") {
         std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
         return 2;
     }
@@ -98,9 +99,11 @@ int main(int argc, char **argv)
         Vol::Rendering::Hip::Camera cam{};
         vr_cam_view(&oc, cam.view);
         vr_cam_position(&oc, cam.position);
-        pass.render_mode_changed(mode == "mip"   ? VR_MODE_MIP
-                                 : mode == "iso" ? VR_MODE_ISO
-                                                 : VR_MODE_COMPOSITE);
+        pass.render_mode_changed(mode == "mip"     ? VR_MODE_MIP
+                                 : mode == "iso"   ? VR_MODE_ISO
+                                 : mode == "minip" ? VR_MODE_MINIP
+                                 : mode == "mean"  ? VR_MODE_MEAN
+                                                   : VR_MODE_COMPOSITE);
         pass.isovalue_changed(iso);  // state: read by iso frames only
         pass.params().shading = shading;
         pass.params().exact_gradient = exact_gradient;

@@ -134,6 +134,7 @@ DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_memb
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
 MODE_COMPOSITE, MODE_MIP = 0, 1
 MODE_ISO = 3  # (2 is unassigned and refused)
+MODE_MINIP, MODE_MEAN = 4, 6  # minimum- and mean-intensity projection (5 is unassigned and refused)
 # include/vr/vr_iso.h: the isovalue of VR_MODE_ISO (context state)
 ISO_SYMBOLS = ["vr_set_isovalue", "vr_get_isovalue"]
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
@@ -538,8 +539,8 @@ class OffscreenPass:
                     "transfer_function_changed")
 
     def render_mode_changed(self, mode: int):
-        """vr_set_render_mode (vr_modes.h): MODE_COMPOSITE, MODE_MIP or MODE_ISO for the frames
-        that follow."""
+        """vr_set_render_mode (vr_modes.h): MODE_COMPOSITE, MODE_MIP, MODE_ISO, MODE_MINIP or
+        MODE_MEAN for the frames that follow."""
         self._check(lib().vr_set_render_mode(self._ctx, int(mode)), "render_mode_changed")
 
     @property
