@@ -1,6 +1,6 @@
 """Reference for the first-hit isosurface (include/vr/vr_iso.h) -- test helper.
 
-The loop of vr_iso.h in np.float32, built like tests/mip_ref.py from the oracle's own pieces:
+The loop of vr_iso.h in np.float32, built like tests/proj_ref.py from the oracle's own pieces:
 Scene.pixel_ray for the entry point and direction, or_trilinear for every sample, or_tf_sample
 for the transfer function.  The gradient and the Phong model are restated here from
 oracle/oracle.c (texel_coord, voxel, dvox, grad_cell, powi, march_pixel_impl's shading) with a

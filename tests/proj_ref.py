@@ -1,15 +1,19 @@
-"""Reference for the minimum- and mean-intensity projections (include/vr/vr_modes.h) -- test
-helper.
+"""Reference for the maximum-, minimum- and mean-intensity projections
+(include/vr/vr_modes.h) -- test helper.
 
-tests/mip_ref.py's loop (the oracle's own pieces: Scene.pixel_ray, or_trilinear, or_tf_sample,
-np.float32 arithmetic for the position update, the bounds break, the strict slab test and the
-blend) keeping another quantity of the ray:
+A float32 restatement of the ray loop of oracle/oracle.c march_pixel_impl built from the
+oracle's own pieces (Scene.pixel_ray for the entry point and direction, or_trilinear for every
+sample, or_tf_sample for the transfer function, np.float32 arithmetic for the position update,
+the bounds break, the strict slab test and the blend), keeping one quantity of the ray and
+looking the TF up once when the ray took an in-slab sample:
 
-  mode="minip"      the smallest sample (np.fmin: a NaN sample leaves it);
+  mode="mip"        the largest sample (np.fmax from -inf: a NaN sample leaves it);
+  mode="minip"      the smallest sample (np.fmin from +inf, likewise);
   mode="mean"       an np.float32 running sum, one addition per in-slab sample in step order,
                     divided by np.float32(n) (the correctly rounded f32 quotient);
   mode="composite"  the reference's composite, which tests/test_proj_cpu.py compares with the C
-                    oracle bit for bit: that pins this loop.
+                    oracle bit for bit (and tests/test_mip_cpu.py): that pins this loop, so the
+                    frames of the other modes can serve as the reference.
 
 It never skips.  order= restates the mean with its additions in another order ("reverse", or
 "batch4": each batch of four summed apart first) -- not a reference, only the proof that the
@@ -32,7 +36,7 @@ import pyoracle
 
 F = np.float32
 PAD, BRICK = 2, 8
-MODES = ("minip", "mean", "composite")
+MODES = ("mip", "minip", "mean", "composite")
 
 
 def brick_grid(n):
@@ -124,10 +128,10 @@ def render(scene, mode="mean", order="step"):
                             ds.append(dv)
                     p0, p1, p2 = p0 + s0, p1 + s1, p2 + s2
                 if ds:
-                    if mode == "minip":
-                        v = F(np.inf)
+                    if mode in ("mip", "minip"):
+                        v, keep = (F(-np.inf), np.fmax) if mode == "mip" else (F(np.inf), np.fmin)
                         for dv in ds:
-                            v = np.fmin(v, dv)
+                            v = keep(v, dv)
                     else:
                         v = _sum(ds, order) / F(len(ds))
                     sc = pyoracle.tf_sample(tf, (v - vmin) / rng)

@@ -4,8 +4,7 @@ The reference is tests/iso_ref.py (the oracle's own ray, filter and TF around th
 search, with the gradient and the Phong model restated from oracle/oracle.c and pinned against
 the C oracle by tests/test_iso_cpu.py); frames must equal it bit for bit in RGBA32F and byte for
 byte in RGBA8, with equal rays, steps, search samples (fetched + skipped) and shaded rays.
-Volumes span three or more bricks per axis with sizes that are no multiple of the brick, frames
-are no multiple of the 16-pixel tile."""
+Scene constants and volumes: tests/range_scenes.py."""
 import os
 import subprocess
 
@@ -16,31 +15,11 @@ import iso_ref
 import pyoracle
 import synth
 import vr_amd
+from range_scenes import CLEAR, FULL, H, SLICE, W, bits, int_volume, volume
 
 pytestmark = pytest.mark.gpu
 
-CLEAR = np.array([0.11, 0.11, 0.11, 1.0], np.float32)
-SLICE = ((0.2, 0.0, 0.1), (0.8, 1.0, 0.9))
 CUT = ((0.45, 0.0, 0.0), (1.0, 1.0, 0.55))
-FULL = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
-W, H = 32, 24
-
-VOLUMES = {
-    "blob16": lambda: synth.gaussian_blob(16),
-    "g20": lambda: synth.gaussians_numpy((20, 18, 22), seed=11),
-    "g13": lambda: synth.gaussians_numpy((13, 7, 21), seed=3),
-}
-_vols = {}
-
-
-def volume(name):
-    if name not in _vols:
-        v = VOLUMES[name]()
-        v.setflags(write=False)
-        _vols[name] = v
-    return _vols[name]
-
-
 def isovalue(v, f):
     lo, hi = float(np.min(v)), float(np.max(v))
     return np.float32(lo + f * (hi - lo))
@@ -72,10 +51,6 @@ def reference(volname, camname, iso, box=FULL, w=W, h=H, shading=1, vol=None, vr
                                           smin=box[0], smax=box[1])
     key = (volname, camname, box, w, h, shading, vrange, tuple(sorted(params.items())))
     return iso_ref.cached(key, make, iso)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
 
 
 def check_against(rp, cam, ref, st, shading=1, skips=(0, 1), **params):
@@ -137,12 +112,6 @@ def test_iso_equals_reference(gpu, volname, camname, box, w, h, f, shading):
 
 
 # ---- 2. storage types and layouts ----------------------------------------------------------------
-def int_volume(signed):
-    g = volume("g20")
-    v = np.rint(g / g.max() * 120.0)
-    return (v - 60.0 if signed else v).astype(np.float32)
-
-
 STORAGE = [  # upload dtype, signed values, knobs, expected storage type, vrange
     (np.uint8, False, dict(u8_layout=0), 0, None), (np.uint8, False, dict(u8_layout=1), 0, None),
     (np.int8, True, dict(u8_layout=0), 1, None), (np.int8, True, dict(u8_layout=1), 1, None),

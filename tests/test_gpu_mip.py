@@ -1,86 +1,22 @@
 """GPU: maximum-intensity projection (include/vr/vr_modes.h, mip_kernel).
 
-The reference is tests/mip_ref.py (the oracle's own ray, filter, TF and blend around np.fmax,
-pinned against the C oracle by tests/test_mip_cpu.py); frames must equal it bit for bit in
-RGBA32F and byte for byte in RGBA8, with equal rays, steps and in-slab samples (fetched +
-skipped).  Volumes span three or more bricks per axis with sizes that are no multiple of the
-brick, frames are no multiple of the 16-pixel tile."""
+The reference is tests/proj_ref.py, mode "mip" (the oracle's own ray, filter, TF and blend around
+np.fmax, pinned against the C oracle by tests/test_mip_cpu.py); frames must equal it bit for bit
+in RGBA32F and byte for byte in RGBA8, with equal rays, steps and in-slab samples (fetched +
+skipped).  Scenes, passes and checks: tests/range_scenes.py."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import mip_ref
 import pyoracle
 import synth
 import vr_amd
+from range_scenes import (CLEAR, FULL, H, SLICE, STORAGE, W, bits, check_against, int_volume, mode_pass,
+                          reference, skip_pair, volume)
 
 pytestmark = pytest.mark.gpu
-
-CLEAR = np.array([0.11, 0.11, 0.11, 1.0], np.float32)
-SLICE = ((0.2, 0.0, 0.1), (0.8, 1.0, 0.9))
-FULL = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
-W, H = 32, 24
-
-VOLUMES = {
-    "blob16": lambda: synth.gaussian_blob(16),
-    "g20": lambda: synth.gaussians_numpy((20, 18, 22), seed=11),
-    "g13": lambda: synth.gaussians_numpy((13, 7, 21), seed=3),
-}
-_vols = {}
-
-
-def volume(name):
-    if name not in _vols:
-        v = VOLUMES[name]()
-        v.setflags(write=False)
-        _vols[name] = v
-    return _vols[name]
-
-
-def mip_pass(w, h, vol, tf, box=FULL, vrange=None, **knobs):
-    rp = vr_amd.OffscreenPass(w, h)
-    for k, v in knobs.items():
-        rp.set_knob(k, v)
-    ds = synth.dataset(np.asarray(vol))
-    if vrange is not None:
-        ds.vmin, ds.vmax = vrange
-    rp.volume_dataset_changed(ds)
-    rp.transfer_function_changed(tf)
-    rp.slicing_changed(*box)
-    rp.render_mode_changed(vr_amd.MODE_MIP)
-    assert rp.render_mode == vr_amd.MODE_MIP
-    return rp
-
-
-def reference(volname, camname, tfname, box=FULL, w=W, h=H, vol=None, vrange=None):
-    """(frame, stats) of mip_ref for a named scene, computed once per session."""
-    def make():
-        v = np.asarray(volume(volname) if vol is None else vol, dtype=np.float32)
-        lo, hi = (float(v.min()), float(v.max())) if vrange is None else vrange
-        return pyoracle.Scene.from_params(v, lo, hi, synth.TFS[tfname](), synth.camera(camname).to_vr_camera(),
-                                          w, h, vr_amd.default_params(), smin=box[0], smax=box[1])
-    return mip_ref.cached((volname, camname, tfname, box, w, h, vrange), make)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def check_against(rp, cam, ref, st, skips=(0, 1)):
-    for skip in skips:
-        p = vr_amd.default_params(skip_empty=skip)
-        img = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        assert np.array_equal(bits(img), bits(ref)), f"skip {skip}: {(bits(img) != bits(ref)).sum()} words differ"
-        img8 = rp.render(cam, p, vr_amd.OUT_RGBA8)
-        assert np.array_equal(img8, vr_amd.unorm8(ref)), f"skip {skip} (RGBA8)"
-        w = rp.count_work(cam, p)
-        assert (w["rays"], w["steps"]) == (st["rays"], st["steps"]), (skip, w, st)
-        assert w["samples"] + w["skipped_samples"] == st["samples"], (skip, w, st)
-        assert w["shaded_samples"] == 0
-        if not skip:
-            assert w["skipped_samples"] == 0
 
 
 # ---- 1. parity --------------------------------------------------------------------------------
@@ -100,8 +36,8 @@ PARITY = [
 
 @pytest.mark.parametrize("volname,camname,tfname,box,w,h", PARITY)
 def test_mip_equals_reference(gpu, volname, camname, tfname, box, w, h):
-    ref, st = reference(volname, camname, tfname, box, w, h)
-    rp = mip_pass(w, h, volume(volname), synth.TFS[tfname](), box)
+    ref, st = reference("mip", volname, camname, tfname, box, w, h)
+    rp = mode_pass("mip", w, h, volume(volname), synth.TFS[tfname](), box)
     try:
         check_against(rp, synth.camera(camname).to_vr_camera(), ref, st)
     finally:
@@ -115,7 +51,7 @@ def test_constant_tf_closed_form(gpu):
     the same scene (its colour differs from the clear colour's exactly there)."""
     tf = np.array([0x80FFFFFF], np.uint32)  # linear white, alpha 128 / 255
     a = np.float32(128.0) / np.float32(255.0)
-    rp = mip_pass(45, 35, volume("g20"), tf, SLICE)
+    rp = mode_pass("mip", 45, 35, volume("g20"), tf, SLICE)
     try:
         cam = synth.camera("fill_oblique").to_vr_camera()
         p = vr_amd.default_params()
@@ -136,7 +72,7 @@ def test_constant_tf_closed_form(gpu):
 
 
 def test_transparent_tf_and_constant_volume(gpu):
-    rp = mip_pass(W, H, volume("g20"), np.zeros(16, np.uint32))
+    rp = mode_pass("mip", W, H, volume("g20"), np.zeros(16, np.uint32))
     try:
         cam = synth.camera("rotA").to_vr_camera()
         for skip in (0, 1):
@@ -146,8 +82,8 @@ def test_transparent_tf_and_constant_volume(gpu):
         rp.close()
     # vmin == vmax: the division gives NaN or an infinity, as in the reference helper
     vol = np.full((9, 10, 11), 0.5, np.float32)
-    ref, st = reference("const", "rotA", "tfc", vol=vol)
-    rp = mip_pass(W, H, vol, synth.tf_color())
+    ref, st = reference("mip", "const", "rotA", "tfc", vol=vol)
+    rp = mode_pass("mip", W, H, vol, synth.tf_color())
     try:
         check_against(rp, synth.camera("rotA").to_vr_camera(), ref, st)
     finally:
@@ -155,27 +91,11 @@ def test_transparent_tf_and_constant_volume(gpu):
 
 
 # ---- 3. storage types ------------------------------------------------------------------------------
-def int_volume(signed):
-    g = volume("g20")
-    v = np.rint(g / g.max() * 120.0)
-    return (v - 60.0 if signed else v).astype(np.float32)
-
-
-STORAGE = [  # upload dtype, signed values, knobs, expected storage type (vr::StorageType)
-    (np.uint8, False, dict(u8_layout=0), 0), (np.uint8, False, dict(u8_layout=1), 0),
-    (np.int8, True, dict(u8_layout=0), 1), (np.int8, True, dict(u8_layout=1), 1),
-    (np.uint16, False, {}, 2), (np.int16, True, {}, 3),
-    (np.float32, True, dict(narrow=0), 4), (np.float32, True, dict(narrow=1, u8_layout=0), 1),
-    (np.int32, False, dict(narrow=1, u8_layout=1), 0), (np.int32, True, dict(narrow=0), 4),
-    (np.float64, True, {}, 4),
-]
-
-
 @pytest.mark.parametrize("dtype,signed,knobs,storage", STORAGE)
 def test_storage_types(gpu, dtype, signed, knobs, storage):
     vf = int_volume(signed)
-    ref, st = reference("int_s" if signed else "int_u", "fill_oblique", "tfc", vol=vf)
-    rp = mip_pass(W, H, vf.astype(dtype), synth.tf_color(), **knobs)
+    ref, st = reference("mip", "int_s" if signed else "int_u", "fill_oblique", "tfc", vol=vf)
+    rp = mode_pass("mip", W, H, vf.astype(dtype), synth.tf_color(), **knobs)
     try:
         assert rp.volume_info()[2] == storage
         check_against(rp, synth.camera("fill_oblique").to_vr_camera(), ref, st)
@@ -184,17 +104,6 @@ def test_storage_types(gpu, dtype, signed, knobs, storage):
 
 
 # ---- 4. range skipping -------------------------------------------------------------------------------
-def skip_pair(rp, cam, fmt=vr_amd.OUT_RGBA32F):
-    a = rp.render(cam, vr_amd.default_params(skip_empty=0), fmt)
-    b = rp.render(cam, vr_amd.default_params(skip_empty=1), fmt)
-    assert np.array_equal(bits(a), bits(b))
-    w0 = rp.count_work(cam, vr_amd.default_params(skip_empty=0))
-    w1 = rp.count_work(cam, vr_amd.default_params(skip_empty=1))
-    assert w0["skipped_samples"] == 0 and (w0["rays"], w0["steps"]) == (w1["rays"], w1["steps"])
-    assert w1["samples"] + w1["skipped_samples"] == w0["samples"]
-    return a, w1
-
-
 @pytest.mark.parametrize("volname,camname", [("blob32", "rotA"), ("g40", "fill")])
 @pytest.mark.parametrize("dtype", [np.float32, np.uint8])
 def test_skipping_is_exact(gpu, volname, camname, dtype):
@@ -206,7 +115,7 @@ def test_skipping_is_exact(gpu, volname, camname, dtype):
     if dtype == np.uint8:
         v = np.rint(v / v.max() * 255.0).astype(np.uint8)
     cam = synth.camera(camname).to_vr_camera()
-    rp = mip_pass(W, H, v, synth.tf2())
+    rp = mode_pass("mip", W, H, v, synth.tf2())
     try:
         first, w = skip_pair(rp, cam)
         print(volname, np.dtype(dtype).name, w)
@@ -242,8 +151,8 @@ def test_skipping_is_exact(gpu, volname, camname, dtype):
 def test_every_inflight_variant_renders_the_same_bytes(gpu, dtype, knobs):
     signed = dtype == np.int16
     vf = int_volume(signed)
-    ref, st = reference("int_s" if signed else "int_u", "fill_oblique", "tfc", vol=vf)
-    rp = mip_pass(45, 35, vf.astype(dtype), synth.tf_color(), **knobs)
+    ref, st = reference("mip", "int_s" if signed else "int_u", "fill_oblique", "tfc", vol=vf)
+    rp = mode_pass("mip", 45, 35, vf.astype(dtype), synth.tf_color(), **knobs)
     try:
         cam = synth.camera("fill_oblique").to_vr_camera()
         frames = {}
@@ -266,7 +175,7 @@ def test_every_inflight_variant_renders_the_same_bytes(gpu, dtype, knobs):
 def test_row_shards_assemble_to_the_full_frame(gpu):
     import torch
     w, h = 75, 53
-    rp = mip_pass(w, h, volume("g20"), synth.tf_color())
+    rp = mode_pass("mip", w, h, volume("g20"), synth.tf_color())
     try:
         cam = synth.camera("rotA").to_vr_camera()
         for skip in (0, 1):
@@ -298,7 +207,7 @@ def test_row_shards_assemble_to_the_full_frame(gpu):
 def test_member_contexts_equal_the_single_context(gpu, members):
     w, h = 75, 61
     vol, tf = volume("g20"), synth.tf_color()
-    one = mip_pass(w, h, vol, tf)
+    one = mode_pass("mip", w, h, vol, tf)
     grp = vr_amd.OffscreenPass(w, h, members=members, exchange=vr_amd.EXCHANGE_COPY)
     try:
         grp.volume_dataset_changed(synth.dataset(np.asarray(vol)))
@@ -322,7 +231,7 @@ def test_member_contexts_equal_the_single_context(gpu, members):
 def test_frames_in_flight_on_three_streams(gpu):
     import torch
     w, h = 75, 53
-    rp = mip_pass(w, h, volume("g20"), synth.tf2())
+    rp = mode_pass("mip", w, h, volume("g20"), synth.tf2())
     try:
         cam = synth.camera("fill_oblique").to_vr_camera()
         for skip in (0, 1):
@@ -344,7 +253,7 @@ def test_frames_in_flight_on_three_streams(gpu):
 def test_host_row_bands_and_kernel_name(gpu):
     import torch
     w, h = 40, 256  # vr_render splits a frame this tall into row bands
-    rp = mip_pass(w, h, volume("g20"), synth.tf_color())
+    rp = mode_pass("mip", w, h, volume("g20"), synth.tf_color())
     try:
         cam = synth.camera("fill").to_vr_camera()
         for skip in (0, 1):

@@ -3,98 +3,23 @@
 The reference is tests/proj_ref.py (the oracle's own ray, filter, TF and blend around np.fmin
 or an f32 running sum in step order, pinned against the C oracle by tests/test_proj_cpu.py);
 frames must equal it bit for bit in RGBA32F and byte for byte in RGBA8, with equal rays, steps
-and in-slab samples (fetched + skipped), for skip_empty 0 and 1.  Volumes span three or more
-bricks per axis with sizes that are no multiple of the brick, frames are no multiple of the
-16-pixel tile."""
+and in-slab samples (fetched + skipped), for skip_empty 0 and 1.  Scenes, passes and checks:
+tests/range_scenes.py."""
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-import proj_ref
-import pyoracle
 import synth
 import vr_amd
-from test_gpu_mip import STORAGE
+from range_scenes import (CLEAR, FULL, H, INSET, SLICE, STORAGE, W, bits, check_against, int_volume,
+                          mode_pass, reference, skip_pair, volume)
 
 pytestmark = pytest.mark.gpu
 
-CLEAR = np.array([0.11, 0.11, 0.11, 1.0], np.float32)
-SLICE = ((0.2, 0.0, 0.1), (0.8, 1.0, 0.9))
-INSET = ((0.06, 0.08, 0.05), (0.94, 0.92, 0.95))  # more than half a voxel of every volume here
-FULL = ((0.0, 0.0, 0.0), (1.0, 1.0, 1.0))
-W, H = 32, 24
 MODES = {"minip": vr_amd.MODE_MINIP, "mean": vr_amd.MODE_MEAN}
 OP = {"minip": 0, "mean": 1}  # proj_kernel's second template argument
-
-
-def plateau():
-    g = synth.gaussians_numpy((40, 36, 44), seed=5)
-    v = (g / g.max()).astype(np.float32)
-    v[v < 0.08] = 0.0
-    return np.minimum(v, np.float32(0.55))
-
-
-VOLUMES = {
-    "blob16": lambda: synth.gaussian_blob(16),
-    "g20": lambda: synth.gaussians_numpy((20, 18, 22), seed=11),
-    "g13": lambda: synth.gaussians_numpy((13, 7, 21), seed=3),
-    "plateau": plateau,
-}
-_vols = {}
-
-
-def volume(name):
-    if name not in _vols:
-        v = VOLUMES[name]()
-        v.setflags(write=False)
-        _vols[name] = v
-    return _vols[name]
-
-
-def proj_pass(mode, w, h, vol, tf, box=FULL, vrange=None, **knobs):
-    rp = vr_amd.OffscreenPass(w, h)
-    for k, v in knobs.items():
-        rp.set_knob(k, v)
-    ds = synth.dataset(np.asarray(vol))
-    if vrange is not None:
-        ds.vmin, ds.vmax = vrange
-    rp.volume_dataset_changed(ds)
-    rp.transfer_function_changed(tf)
-    rp.slicing_changed(*box)
-    rp.render_mode_changed(MODES[mode])
-    assert rp.render_mode == MODES[mode]
-    return rp
-
-
-def reference(mode, volname, camname, tfname, box=FULL, w=W, h=H, vol=None, vrange=None):
-    """(frame, stats) of proj_ref for a named scene, computed once per session."""
-    def make():
-        v = np.asarray(volume(volname) if vol is None else vol, dtype=np.float32)
-        lo, hi = (float(np.nanmin(v)), float(np.nanmax(v))) if vrange is None else vrange
-        return pyoracle.Scene.from_params(v, lo, hi, synth.TFS[tfname](), synth.camera(camname).to_vr_camera(),
-                                          w, h, vr_amd.default_params(), smin=box[0], smax=box[1])
-    return proj_ref.cached((volname, camname, tfname, box, w, h, vrange), make, mode)
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint8)
-
-
-def check_against(rp, cam, ref, st, skips=(0, 1)):
-    for skip in skips:
-        p = vr_amd.default_params(skip_empty=skip)
-        img = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        assert np.array_equal(bits(img), bits(ref)), f"skip {skip}: {(bits(img) != bits(ref)).sum()} words differ"
-        img8 = rp.render(cam, p, vr_amd.OUT_RGBA8)
-        assert np.array_equal(img8, vr_amd.unorm8(ref)), f"skip {skip} (RGBA8)"
-        w = rp.count_work(cam, p)
-        assert (w["rays"], w["steps"]) == (st["rays"], st["steps"]), (skip, w, st)
-        assert w["samples"] + w["skipped_samples"] == st["samples"], (skip, w, st)
-        assert w["shaded_samples"] == 0
-        if not skip:
-            assert w["skipped_samples"] == 0
 
 
 # ---- 1. parity --------------------------------------------------------------------------------
@@ -125,7 +50,7 @@ PARITY = [  # MinIP mostly with an inset box: what the mode is for
 @pytest.mark.parametrize("mode,volname,camname,tfname,box,w,h", PARITY)
 def test_projection_equals_reference(gpu, mode, volname, camname, tfname, box, w, h):
     ref, st = reference(mode, volname, camname, tfname, box, w, h)
-    rp = proj_pass(mode, w, h, volume(volname), synth.TFS[tfname](), box)
+    rp = mode_pass(mode, w, h, volume(volname), synth.TFS[tfname](), box)
     try:
         check_against(rp, synth.camera(camname).to_vr_camera(), ref, st)
     finally:
@@ -144,7 +69,7 @@ def test_constant_volume_closed_form(gpu):
     cam = synth.camera("fill_oblique").to_vr_camera()
     a = np.float32(128.0) / np.float32(255.0)
     for tf in (np.array([0x80FFFFFF], np.uint32), synth.tf2()):
-        rp = proj_pass("mean", 45, 35, vol, tf, box, vrange=(0.0, 1.0))
+        rp = mode_pass("mean", 45, 35, vol, tf, box, vrange=(0.0, 1.0))
         try:
             frames = {}
             for mode in (vr_amd.MODE_MEAN, vr_amd.MODE_MINIP, vr_amd.MODE_MIP):
@@ -171,7 +96,7 @@ def test_constant_volume_closed_form(gpu):
 
 @pytest.mark.parametrize("mode", MODES)
 def test_transparent_tf_and_flat_range(gpu, mode):
-    rp = proj_pass(mode, W, H, volume("g20"), np.zeros(16, np.uint32))
+    rp = mode_pass(mode, W, H, volume("g20"), np.zeros(16, np.uint32))
     try:
         cam = synth.camera("rotA").to_vr_camera()
         for skip in (0, 1):
@@ -182,7 +107,7 @@ def test_transparent_tf_and_flat_range(gpu, mode):
     # vmin == vmax: the division gives NaN or an infinity, as in the reference helper
     vol = np.full((9, 10, 11), 0.5, np.float32)
     ref, st = reference(mode, "const", "rotA", "tfc", vol=vol)
-    rp = proj_pass(mode, W, H, vol, synth.tf_color())
+    rp = mode_pass(mode, W, H, vol, synth.tf_color())
     try:
         check_against(rp, synth.camera("rotA").to_vr_camera(), ref, st)
     finally:
@@ -190,18 +115,12 @@ def test_transparent_tf_and_flat_range(gpu, mode):
 
 
 # ---- 3. storage types ------------------------------------------------------------------------------
-def int_volume(signed):
-    g = volume("g20")
-    v = np.rint(g / g.max() * 120.0)
-    return (v - 60.0 if signed else v).astype(np.float32)
-
-
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("dtype,signed,knobs,storage", STORAGE)
 def test_storage_types(gpu, mode, dtype, signed, knobs, storage):
     vf = int_volume(signed)
     ref, st = reference(mode, "int_s" if signed else "int_u", "fill_oblique", "tfc", INSET, vol=vf)
-    rp = proj_pass(mode, W, H, vf.astype(dtype), synth.tf_color(), INSET, **knobs)
+    rp = mode_pass(mode, W, H, vf.astype(dtype), synth.tf_color(), INSET, **knobs)
     try:
         assert rp.volume_info()[2] == storage
         check_against(rp, synth.camera("fill_oblique").to_vr_camera(), ref, st)
@@ -217,7 +136,7 @@ def test_every_inflight_variant_renders_the_same_bytes(gpu, mode, dtype, knobs):
     signed = dtype == np.int16
     vf = int_volume(signed)
     ref, st = reference(mode, "int_s" if signed else "int_u", "fill_oblique", "tfc", INSET, vol=vf)
-    rp = proj_pass(mode, 45, 35, vf.astype(dtype), synth.tf_color(), INSET, **knobs)
+    rp = mode_pass(mode, 45, 35, vf.astype(dtype), synth.tf_color(), INSET, **knobs)
     try:
         cam = synth.camera("fill_oblique").to_vr_camera()
         frames = {}
@@ -240,18 +159,6 @@ def test_every_inflight_variant_renders_the_same_bytes(gpu, mode, dtype, knobs):
 
 
 # ---- 5. range skipping -------------------------------------------------------------------------------
-def skip_pair(rp, cam, fmt=vr_amd.OUT_RGBA32F):
-    a = rp.render(cam, vr_amd.default_params(skip_empty=0), fmt)
-    b = rp.render(cam, vr_amd.default_params(skip_empty=1), fmt)
-    assert np.array_equal(bits(a), bits(b))
-    w0 = rp.count_work(cam, vr_amd.default_params(skip_empty=0))
-    w1 = rp.count_work(cam, vr_amd.default_params(skip_empty=1))
-    assert w0["skipped_samples"] == 0 and (w0["rays"], w0["steps"]) == (w1["rays"], w1["steps"])
-    assert w1["samples"] + w1["skipped_samples"] == w0["samples"]
-    assert w0["shaded_samples"] == 0 == w1["shaded_samples"]
-    return a, w1
-
-
 def model_skips(volname, vol, camname, box, vrange=None):
     """In-slab samples in constant bricks, from the helper's model of the stored f32 ranges."""
     return reference("mean", volname, camname, "tf2", box, vol=vol, vrange=vrange)[1]["const_samples"]
@@ -272,7 +179,7 @@ def test_skipping_is_exact(gpu, mode, dtype, camname):
     if dtype == np.uint8:
         v = np.rint(v / v.max() * 255.0).astype(np.uint8)
     cam = synth.camera(camname).to_vr_camera()
-    rp = proj_pass(mode, W, H, v, synth.tf2())
+    rp = mode_pass(mode, W, H, v, synth.tf2())
     try:
         first, w = skip_pair(rp, cam)
         print(mode, camname, np.dtype(dtype).name, w)
@@ -327,7 +234,7 @@ def test_skipping_is_exact(gpu, mode, dtype, camname):
 def test_row_shards_assemble_to_the_full_frame(gpu, mode):
     import torch
     w, h = 75, 53
-    rp = proj_pass(mode, w, h, volume("g20"), synth.tf_color(), INSET)
+    rp = mode_pass(mode, w, h, volume("g20"), synth.tf_color(), INSET)
     try:
         cam = synth.camera("rotA").to_vr_camera()
         for skip in (0, 1):
@@ -389,7 +296,7 @@ def test_member_contexts_equal_the_single_context(gpu, members):
 def test_frames_in_flight_on_three_streams(gpu, mode):
     import torch
     w, h = 75, 53
-    rp = proj_pass(mode, w, h, volume("g20"), synth.tf_color(), INSET)
+    rp = mode_pass(mode, w, h, volume("g20"), synth.tf_color(), INSET)
     try:
         cam = synth.camera("fill_oblique").to_vr_camera()
         for skip in (0, 1):
@@ -460,7 +367,7 @@ def test_mode_round_trips_leave_the_other_modes_untouched(gpu):
 def test_host_row_bands_prepare_and_timing(gpu):
     import torch
     w, h = 40, 256  # vr_render splits a frame this tall into row bands
-    rp = proj_pass("mean", w, h, volume("g20"), synth.tf_color())
+    rp = mode_pass("mean", w, h, volume("g20"), synth.tf_color())
     try:
         cam = synth.camera("fill").to_vr_camera()
         for mode in MODES:

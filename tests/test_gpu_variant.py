@@ -14,7 +14,7 @@ import re
 import numpy as np
 import pytest
 
-import mip_ref
+import proj_ref
 import pyoracle
 import synth
 import vr_amd
@@ -66,7 +66,7 @@ def mip_oracle(vol):
         return pyoracle.Scene.from_params(v, float(v.min()), float(v.max()), TFS[256],
                                           synth.camera(MIP_CAM).to_vr_camera(), W, H,
                                           vr_amd.default_params())
-    return mip_ref.cached(("variant", vol, MIP_CAM, W, H), make)[0]
+    return proj_ref.cached(("variant", vol, MIP_CAM, W, H), make, "mip")[0]
 
 
 def same_bits(img, ref):

@@ -1,4 +1,4 @@
-"""CPU: the render-mode ABI (include/vr/vr_modes.h) and the MIP reference helper.
+"""CPU: the render-mode ABI (include/vr/vr_modes.h) and the reference helper's MIP mode.
 
 No compute calls (no GPU in the build container): exported symbols, argument checks, the
 unchanged ABI version, the helper's own loop pinned against the C oracle, and the C++ shim's
@@ -11,7 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import mip_ref
+import proj_ref
 import pyoracle
 import synth
 import vr_amd
@@ -68,16 +68,16 @@ def test_abi_version_is_unchanged():
 @pytest.mark.parametrize("camname,box,rays,empty", [("rotA", ((0, 0, 0), (1, 1, 1)), 443, None),
                                                     ("fill_oblique", SLICE, 698, 303)])
 def test_reference_loop_reproduces_the_oracle_composite(camname, box, rays, empty):
-    """mip_ref's loop in composite mode is the C oracle bit for bit: same frame, same counters."""
+    """proj_ref's loop in composite mode is the C oracle bit for bit: same frame, same counters."""
     sc = scene(camname, smin=box[0], smax=box[1])
     ref, st = sc.render()
-    got, gs = mip_ref.render(sc, mode="composite")
+    got, gs = proj_ref.render(sc, mode="composite")
     assert st["rays"] == rays == gs["rays"]
     assert gs["steps"] == st["steps"] and gs["samples"] == st["samples"]
     assert np.array_equal(got.view(np.uint32), ref.view(np.uint32))
     if empty is not None:  # rays that cross the cube but never the slice box keep the clear colour
         clear = np.array([0.11, 0.11, 0.11, 1.0], np.float32)
-        mip, ms = mip_ref.render(sc, mode="mip")
+        mip, ms = proj_ref.render(sc, mode="mip")
         assert ms == gs
         untouched = np.all(mip == clear, axis=-1).sum() - (W * H - rays)
         assert untouched == empty
@@ -90,7 +90,7 @@ def test_reference_mip_closed_form():
     tf = np.array([0x80FFFFFF], np.uint32)  # white, alpha 128/255
     cam = synth.camera("rotA").to_vr_camera()
     sc = pyoracle.Scene.from_params(vol, 0.0, 1.0, tf, cam, 16, 12, vr_amd.default_params())
-    img, st = mip_ref.render(sc)
+    img, st = proj_ref.render(sc, mode="mip")
     a = 128.0 / 255.0
     hit = img[..., 3] != 1.0
     assert 0 < hit.sum() <= st["rays"]

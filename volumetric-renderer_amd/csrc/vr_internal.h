@@ -460,7 +460,8 @@ struct IsoArgs {
 // ---- Minimum- and mean-intensity projection (include/vr/vr_modes.h, proj_kernel) ----
 // What proj_kernel reads beside MarchParams (its own argument, as MipArgs): the brick ranges of
 // MipArgs, null without range skipping.  MinIP reads .x of the entry after the last brick, the
-// smallest lo of all.
+// smallest lo of all.  Also what proj_strip takes: mip_kernel runs it with the maximum as its
+// operator (kProjMax, vr_variant.h) and hands its MipArgs on as these.
 struct ProjArgs {
     const float2 *brick_range;
     uint32_t nbricks;

@@ -1100,7 +1100,7 @@ __device__ __forceinline__ void shade_sample(const MarchParams &P, const char *_
 
 // ---- what the frame kernels share: a lane's pixel, the pixel's epilogue, the tile's frame ------
 // (The ray walk itself -- position update, bounds break, slab test -- stays spelled out in each
-// of march_strip, mip_strip, iso_strip and march_pair_kernel: every shared form of it tried
+// of march_strip, proj_strip, iso_strip and march_pair_kernel: every shared form of it tried
 // moved the composite kernels' machine code or the range kernels' registers; CHANGELOG.)
 
 // Row ly of this rank's share of the frame -> the frame's row gy (vr_internal.h RowShare);
@@ -1512,28 +1512,47 @@ __global__ __launch_bounds__(kThreadsPerTile, (SHADE ? 6 : kMarchMinWaves<false,
     march_tile<VT, SHADE, false, false, SHADE, true>(P, s_tf, tile_x, tile_y, wall_clock64());
 }
 
-// ---- maximum-intensity projection (include/vr/vr_modes.h) ------------------------------------
+// ---- maximum-, minimum- and mean-intensity projection (include/vr/vr_modes.h) ----------------
 // The same ray as march_strip (pixel_ray, nsteps, the f32 position update, the bounds break and
-// the strict slab test), but a pixel keeps the largest trilinear sample m of its ray and reads
-// the TF once, at m: one composite step from T = 1 over the clear colour.  fmaxf is exact and
-// commutative and ignores a NaN operand, so the order the samples are taken in, and which of
-// them are proven not to exceed the running maximum and left out, never shows in the frame.
-// There is no dependent chain between samples: K steps' loads are issued before any of them is
-// filtered (lanes whose ray has ended, or whose sample is off-slab or skipped, load element 0
-// of the volume, one cached line, so the loads stay unconditional).
+// the strict slab test), but a pixel keeps one quantity v of its ray's trilinear samples and
+// reads the TF once, at v: one composite step from T = 1 over the clear colour.  There is no
+// dependent chain between samples: K steps' loads are issued before any of them is filtered
+// (lanes whose ray has ended, or whose sample is off-slab or skipped, load element 0 of the
+// volume, one cached line, so the loads stay unconditional; with SKIP a step no lane of the
+// wave fetches issues no load).  mip_kernel runs OP = kProjMax, proj_kernel the other two.
 //
-// SKIP: a sample whose brick's stored maximum hi (brick_range_kernel: every value a sample in
-// the brick can read, apron and zero border included) is not above the ray's running maximum
-// is not fetched.  Exact: a sample is three levels of fmaf(w, b - a, a) with w in [0, 1].  For
-// 8/16-bit voxels b - a is exact, so each level is the correctly rounded value of a point
-// between a and b and cannot pass max(a, b): tri <= hi.  For f32 voxels b - a rounds, and with
-// w = 1 (u - floor(u) rounds up to 1 just below a voxel centre) a level can pass max(a, b) by
-// an ulp of the larger operand, so hi is widened by the classifier's margin (classify_kernel,
-// 4e-6 (|lo| + |hi|), three orders above the three roundings; infinite when b - a can
-// overflow).  !(hi <= m) keeps NaN bricks.  The test reads m as it stood before the batch of K
-// steps: any earlier value of the maximum proves the same.  A ray of an 8/16-bit volume ends
-// once m reaches the largest hi of the volume.
-// COUNT: walks every step, fetches and skips per lane, and fills vr_stats (shaded 0).
+// OP = kProjMax: v is the largest sample, m = fmaxf(m, d) from -INFINITY.  fmaxf is exact and
+// commutative and ignores a NaN operand, so the order the samples are taken in, K, and which
+// samples are proven not to exceed the running maximum and left out, never show in the frame.
+//   SKIP: a sample whose brick's stored maximum hi (brick_range_kernel: every value a sample in
+//   the brick can read, apron and zero border included) is not above the ray's running maximum
+//   is not fetched.  Exact: a sample is three levels of fmaf(w, b - a, a) with w in [0, 1].  For
+//   8/16-bit voxels b - a is exact, so each level is the correctly rounded value of a point
+//   between a and b and cannot pass max(a, b): tri <= hi.  For f32 voxels b - a rounds, and with
+//   w = 1 (u - floor(u) rounds up to 1 just below a voxel centre) a level can pass max(a, b) by
+//   an ulp of the larger operand, so hi is widened by the classifier's margin (classify_kernel,
+//   4e-6 (|lo| + |hi|), three orders above the three roundings; infinite when b - a can
+//   overflow).  !(hi <= m) keeps NaN bricks.  The test reads m as it stood before the batch of
+//   K steps: any earlier value of the maximum proves the same.  A ray of an 8/16-bit volume
+//   ends once m reaches the largest hi of the volume (the entry after the last brick).
+// OP = kProjMin: the mirror image, m = fminf(m, d) from +INFINITY.  The bound is the brick's
+//   stored minimum lo, lowered for f32 by the same margin (-INFINITY when b - a can overflow):
+//   tri >= lo by the argument above with min(a, b) for max(a, b).  !(lo >= m) keeps NaN bricks,
+//   and the ray ends once m reaches the smallest lo of the volume (then a sample was taken: m
+//   is finite only after one).
+// OP = kProjMean: v = sum / (float)n, sum one f32 addition per in-slab sample from +0.  The
+// order of the additions is part of the result: the consume half of a batch adds its K samples
+// in step order into the one running sum, so every K gives the reference's bits.
+//   SKIP: a sample whose brick has lo == hi, finite, is not fetched and adds lo at its step's
+//   place (it counts in n).  Exact: every voxel the sample can read is c = lo, each lerp level
+//   is fmaf(w, c - c, c) = fmaf(w, 0, c) = c for finite c.  An infinite c gives inf - inf =
+//   NaN, so such a brick is fetched; a NaN brick stores (NaN, NaN) and lo == hi is false.  A
+//   brick of mixed +0 / -0 also has lo == hi and adds a zero of either sign where the filter
+//   gives one of either sign: x + (+-0) = x for x != 0, +0 + (+-0) = +0, and a sum that
+//   started at +0 is never -0 (two operands sum to -0 only when both are -0), so the sign
+//   never shows.  There is no early end.
+// COUNT: walks every step, fetches and skips per lane, and fills vr_stats (shaded 0); samples +
+// skipped is the number of in-slab steps.
 template <typename VT>
 constexpr bool kMipQuadRaw = !kZPair<VT> && !kPlainByte<VT>;
 template <typename VT, typename = void>
@@ -1567,188 +1586,50 @@ struct MipRaw<VT, std::enable_if_t<kMipQuadRaw<VT>>> {
     }
 };
 
-template <typename VT, bool COUNT, bool SKIP, int K>
-__device__ __forceinline__ void mip_strip(const MarchParams &P, const MipArgs &M, uint32_t tile_x,
-                                          uint32_t tile_y, uint32_t wave, uint32_t lane)
-{
-    using G = GeomOf<VT>;
-    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
-
-    float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
-    const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
-
-    float m = -INFINITY;
-    bool any = false;
-    unsigned long long n_samples = 0, n_steps = 0, n_skipped = 0;
-    uint32_t cur_brick = 0xFFFFFFFFu;
-    float cur_hi = INFINITY;
-    const char *__restrict__ vol = static_cast<const char *>(P.vol);
-    const int nsteps = covered ? P.nsteps : 0;
-    float p0 = tex[0], p1 = tex[1], p2 = tex[2];
-    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
-    const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
-    float end_at = INFINITY;  // 8/16-bit volumes: no sample exceeds the largest brick maximum
-    if constexpr (SKIP && !COUNT && !kZPair<VT>) end_at = M.brick_range[M.nbricks].y;
-
-    struct Stage {
-        MipRaw<VT> r;
-        float ax, ay, az;
-        bool fetch, issued;
-    };
-    bool live = nsteps > 0;
-    for (int it = 0; live; it += K) {
-        Stage S[K];
-        const float m_in = m;
-#pragma unroll
-        for (int s = 0; s < K; ++s) {
-            const int k = it + s;
-            const bool interior = (unsigned)(k - 1) < (unsigned)kin;
-            // volume.frag:34-37: the first position outside ends the ray
-            live = live && k < nsteps &&
-                   (interior || !(p0 > 1.0f || p1 > 1.0f || p2 > 1.0f || p0 < 0.0f || p1 < 0.0f ||
-                                  p2 < 0.0f));
-            if (COUNT && live) ++n_steps;
-            // volume.frag:39-40 (strict)
-            const bool slab = live && (interior || (p0 < P.smax[0] && p1 < P.smax[1] &&
-                                                    p2 < P.smax[2] && p0 > P.smin[0] &&
-                                                    p1 > P.smin[1] && p2 > P.smin[2]));
-            int i, j, kk;
-            texel_coord(p0, P.fnx, i, S[s].ax);
-            texel_coord(p1, P.fny, j, S[s].ay);
-            texel_coord(p2, P.fnz, kk, S[s].az);
-            const int pi = i + kPad, pj = j + kPad, pk = kk + kPad;
-            bool fetch = slab;
-            if constexpr (SKIP) {
-                if (slab) {
-                    const uint32_t bb = ((uint32_t)pk / G::BZ * P.nby + (uint32_t)pj / G::BY) * P.nbx +
-                                        (uint32_t)pi / G::BX;
-                    if (bb != cur_brick) {
-                        cur_brick = bb;
-                        const float2 r = VR_OOB(7, bb, M.nbricks) ? make_float2(NAN, NAN)
-                                                                   : M.brick_range[bb];
-                        cur_hi = kZPair<VT> ? r.y + (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.y;
-                    }
-                    fetch = !(cur_hi <= m_in);
-                }
-            }
-            if (COUNT && slab) {
-                if (fetch)
-                    ++n_samples;
-                else
-                    ++n_skipped;
-            }
-            any = any || slab;
-            S[s].fetch = fetch;
-            size_t ce = fetch ? cell_offset<VT>(pi, pj, pk, P.nbx, P.nby) : (size_t)0;
-            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
-            // without SKIP every step loads; with it a step no lane of the wave fetches does not
-            S[s].issued = !SKIP || __any(fetch);
-            if (S[s].issued) S[s].r.issue(vol, ce);
-            // volume.frag:47
-            p0 = p0 + d0 * P.step;
-            p1 = p1 + d1 * P.step;
-            p2 = p2 + d2 * P.step;
-        }
-#pragma unroll
-        for (int s = 0; s < K; ++s) {
-            if (S[s].issued) {
-                Cell8<VT> c;
-                S[s].r.decode(c);
-                const float d = c.tri(S[s].ax, S[s].ay, S[s].az);
-                if (S[s].fetch) m = fmaxf(m, d);  // a NaN sample leaves m
-            }
-        }
-        if (!COUNT && m >= end_at) live = false;
-    }
-
-    if (COUNT) flush_counters(P, lane, covered, n_samples, 0, n_steps, n_skipped);
-    if (!pix.active) return;
-
-    // one composite step from T = 1 (volume.frag:42-45), then the blend over the clear colour
-    float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
-    if (any) {
-        const float tt = div_by_range(m - P.vmin, P);
-        const float4 s = tf_lookup(P.tf, P.tf_n, P.tf_nf, tt);
-        cr = (s.x * s.w) * 1.0f;
-        cg = (s.y * s.w) * 1.0f;
-        cb = (s.z * s.w) * 1.0f;
-        T = 1.0f * (1.0f - s.w);
-    }
-    store_pixel(P, pix.px, pix.ly, blend_over_clear(P, cr, cg, cb, T));
-}
-
-template <typename VT, bool COUNT, bool SKIP, int K>
-__global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams P, const MipArgs M)
-{
-    const int tid = threadIdx.x;
-    uint32_t tile_x, tile_y;
-    if (!block_tile(P, tile_x, tile_y)) return;
-    const long long wg_start = wall_clock64();
-    mip_strip<VT, COUNT, SKIP, K>(P, M, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
-    write_tile_cost(P, tile_x, tile_y, wg_start);
-}
-
-// ---- minimum- and mean-intensity projection (include/vr/vr_modes.h) --------------------------
-// mip_strip's ray and batch loop (K steps' loads issued before any is filtered; dead, off-slab
-// and skipped lanes load element 0; with SKIP a step no lane fetches issues no load), keeping
-// another quantity of the ray.  The pixel reads the TF once, at v, with MIP's epilogue.
-//
-// OP = kProjMin: v is the smallest sample, m = fminf(m, d) from +INFINITY.  fminf is exact and
-// commutative and ignores a NaN operand, so neither the order nor K shows in the frame.
-//   SKIP mirrors MIP's: a sample whose brick's stored minimum lo is not below the running
-//   minimum is not fetched.  8/16-bit voxels: b - a is exact, so each lerp level is the
-//   correctly rounded value of a point between a and b and cannot pass below min(a, b):
-//   tri >= lo.  f32: a level can pass min(a, b) by an ulp of the larger operand, so lo is
-//   lowered by the classifier's margin 4e-6 (|lo| + |hi|) (-INFINITY when b - a can overflow).
-//   !(lo >= m) keeps NaN bricks; m is read as it stood before the batch.  A ray of an 8/16-bit
-//   volume ends once m reaches the smallest lo of the volume (then a sample was taken: m is
-//   finite only after one).
-// OP = kProjMean: v = sum / (float)n, sum one f32 addition per in-slab sample from +0.  The
-// order of the additions is part of the result: the consume half of a batch adds its K samples
-// in step order into the one running sum, so every K gives the reference's bits.
-//   SKIP: a sample whose brick has lo == hi, finite, is not fetched and adds lo at its step's
-//   place (it counts in n).  Exact: every voxel the sample can read is c = lo, each lerp level
-//   is fmaf(w, c - c, c) = fmaf(w, 0, c) = c for finite c.  An infinite c gives inf - inf =
-//   NaN, so such a brick is fetched; a NaN brick stores (NaN, NaN) and lo == hi is false.  A
-//   brick of mixed +0 / -0 also has lo == hi and adds a zero of either sign where the filter
-//   gives one of either sign: x + (+-0) = x for x != 0, +0 + (+-0) = +0, and a sum that
-//   started at +0 is never -0 (two operands sum to -0 only when both are -0), so the sign
-//   never shows.  There is no early end.
-// COUNT: walks every step, fetches and skips per lane, and fills vr_stats (shaded 0); samples +
-// skipped is the number of in-slab steps.
 template <typename VT, int OP, bool COUNT, bool SKIP, int K>
 __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs &M, uint32_t tile_x,
                                            uint32_t tile_y, uint32_t wave, uint32_t lane)
 {
-    static_assert(OP == kProjMin || OP == kProjMean, "minimum or mean");
+    static_assert(OP == kProjMin || OP == kProjMean || OP == kProjMax, "minimum, mean or maximum");
     static_assert(!COUNT || K == 1, "the counting kernels walk one step at a time");
-    constexpr bool MEAN = OP == kProjMean;
+    constexpr bool MEAN = OP == kProjMean, MAX = OP == kProjMax;
     using G = GeomOf<VT>;
     const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
 
     float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
     const bool covered = pix.active && pixel_ray(P, pix.px, pix.gy, tex, dir);
 
-    float m = MEAN ? 0.0f : INFINITY;  // the running minimum, or the running sum
-    int n = 0;                         // mean: in-slab samples so far
+    float m = MEAN ? 0.0f : MAX ? -INFINITY : INFINITY;  // the running sum, maximum or minimum
+    int n = 0;                                           // mean: in-slab samples so far
     bool any = false;
     unsigned long long n_samples = 0, n_steps = 0, n_skipped = 0;
     uint32_t cur_brick = 0xFFFFFFFFu;
-    float cur_lo = MEAN ? NAN : -INFINITY;  // min: the brick's (lowered) lo; mean: its constant or NaN
+    // max / min: the brick's (widened) hi / (lowered) lo; mean: its constant or NaN
+    float cur_bound = MEAN ? NAN : MAX ? INFINITY : -INFINITY;
     const char *__restrict__ vol = static_cast<const char *>(P.vol);
     const int nsteps = covered ? P.nsteps : 0;
     float p0 = tex[0], p1 = tex[1], p2 = tex[2];
     const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
     const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
-    float end_at = -INFINITY;  // 8/16-bit volumes: no sample is below the smallest brick minimum
-    if constexpr (!MEAN && SKIP && !COUNT && !kZPair<VT>) end_at = M.brick_range[M.nbricks].x;
+    // 8/16-bit volumes: no sample is above the largest brick maximum / below the smallest minimum
+    float end_at = MAX ? INFINITY : -INFINITY;
+    if constexpr (!MEAN && SKIP && !COUNT && !kZPair<VT>)
+        end_at = MAX ? M.brick_range[M.nbricks].y : M.brick_range[M.nbricks].x;
 
-    struct Stage {
+    // The maximum keeps its own Stage and takes its sample inside the issued branch, as
+    // mip_kernel did before it ran this strip: with the minimum's forms 42 of the 56 mip_kernel
+    // come out in another instruction order and the skipping ones run 1-3 % slower
+    // (profiles/r12/proj_max/); so they are the same machine code as before.
+    struct StageMax {
         MipRaw<VT> r;
         float ax, ay, az;
-        float c;  // mean with SKIP: what a sample that is not fetched adds
-        bool slab, fetch, issued;
+        bool fetch, issued;
     };
+    struct StageSlab : StageMax {
+        float c;  // mean with SKIP: what a sample that is not fetched adds
+        bool slab;
+    };
+    using Stage = std::conditional_t<MAX, StageMax, StageSlab>;
     bool live = nsteps > 0;
     for (int it = 0; live; it += K) {
         Stage S[K];
@@ -1781,13 +1662,17 @@ __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs 
                         const float2 r = VR_OOB(7, bb, M.nbricks) ? make_float2(NAN, NAN)
                                                                    : M.brick_range[bb];
                         if constexpr (MEAN)
-                            cur_lo = (r.x == r.y && fabsf(r.x) < INFINITY) ? r.x : NAN;
+                            cur_bound = (r.x == r.y && fabsf(r.x) < INFINITY) ? r.x : NAN;
+                        else if constexpr (MAX)
+                            cur_bound = kZPair<VT> ? r.y + (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.y;
                         else
-                            cur_lo = kZPair<VT> ? r.x - (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.x;
+                            cur_bound = kZPair<VT> ? r.x - (fabsf(r.x) + fabsf(r.y)) * 4.0e-6f : r.x;
                     }
-                    fetch = MEAN ? cur_lo != cur_lo : !(cur_lo >= m_in);
+                    fetch = MEAN  ? cur_bound != cur_bound
+                            : MAX ? !(cur_bound <= m_in)
+                                  : !(cur_bound >= m_in);
                 }
-                S[s].c = cur_lo;
+                if constexpr (!MAX) S[s].c = cur_bound;
             }
             if (COUNT && slab) {
                 if (fetch)
@@ -1796,7 +1681,7 @@ __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs 
                     ++n_skipped;
             }
             any = any || slab;
-            S[s].slab = slab;
+            if constexpr (!MAX) S[s].slab = slab;
             S[s].fetch = fetch;
             size_t ce = fetch ? cell_offset<VT>(pi, pj, pk, P.nbx, P.nby) : (size_t)0;
             if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
@@ -1815,6 +1700,8 @@ __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs 
                 Cell8<VT> c;
                 S[s].r.decode(c);
                 d = c.tri(S[s].ax, S[s].ay, S[s].az);
+                if constexpr (MAX)
+                    if (S[s].fetch) m = fmaxf(m, d);  // a NaN sample leaves m
             }
             if constexpr (MEAN) {
                 if constexpr (SKIP) d = S[s].fetch ? d : S[s].c;
@@ -1822,11 +1709,11 @@ __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs 
                     m = m + d;
                     ++n;
                 }
-            } else {
+            } else if constexpr (!MAX) {
                 if (S[s].fetch) m = fminf(m, d);  // a NaN sample leaves m
             }
         }
-        if (!MEAN && !COUNT && m <= end_at) live = false;
+        if (!MEAN && !COUNT && (MAX ? m >= end_at : m <= end_at)) live = false;
     }
 
     if (COUNT) flush_counters(P, lane, covered, n_samples, 0, n_steps, n_skipped);
@@ -1846,6 +1733,18 @@ __device__ __forceinline__ void proj_strip(const MarchParams &P, const ProjArgs 
     store_pixel(P, pix.px, pix.ly, blend_over_clear(P, cr, cg, cb, T));
 }
 
+template <typename VT, bool COUNT, bool SKIP, int K>
+__global__ __launch_bounds__(kThreadsPerTile) void mip_kernel(const MarchParams P, const MipArgs M)
+{
+    const int tid = threadIdx.x;
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    const long long wg_start = wall_clock64();
+    proj_strip<VT, kProjMax, COUNT, SKIP, K>(P, ProjArgs{M.brick_range, M.nbricks}, tile_x, tile_y,
+                                             (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    write_tile_cost(P, tile_x, tile_y, wg_start);
+}
+
 template <typename VT, int OP, bool COUNT, bool SKIP, int K>
 __global__ __launch_bounds__(kThreadsPerTile) void proj_kernel(const MarchParams P, const ProjArgs M)
 {
@@ -1858,19 +1757,19 @@ __global__ __launch_bounds__(kThreadsPerTile) void proj_kernel(const MarchParams
 }
 
 // ---- first-hit isosurface (include/vr/vr_iso.h) ----------------------------------------------
-// The same ray as march_strip and mip_strip, but the pixel shows the first in-slab sample whose
+// The same ray as march_strip and proj_strip, but the pixel shows the first in-slab sample whose
 // density reaches the isovalue: a search with an ordered early exit, then -- once the whole
 // wavefront has left the search loop -- four bisection fetches between the last sample below
 // (q) and the hit, one gradient from the base bricks (the exact f32 central differences of
 // gradient<VT>, never the binary16 field) and the composite's Phong; the pixel is opaque.
-// The search loop is mip_strip's: K steps' loads are issued before any is filtered, lanes
+// The search loop is proj_strip's: K steps' loads are issued before any is filtered, lanes
 // whose ray has ended or whose sample is off-slab or skipped load element 0.  Unlike the
 // maximum the result depends on the order: the samples of a batch are examined in step order
 // behind a position cursor that repeats the ray's own additions, the hit is the lowest step
 // that passes, q the in-slab step before it (possibly of the previous batch), and what the
 // batch loaded beyond the hit is dropped.  So the frame is the same for every K.
 //
-// SKIP: a sample whose brick's stored maximum hi (widened for f32 as mip_strip's, by the same
+// SKIP: a sample whose brick's stored maximum hi (widened for f32 as proj_strip's, by the same
 // argument: every sample in the brick is <= hi) is below the isovalue cannot hit and is not
 // fetched; it still counts as a sample below (prev, q).  !(hi < iso) keeps NaN bricks, and a
 // NaN sample never hits (d >= iso is false).

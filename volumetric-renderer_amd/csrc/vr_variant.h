@@ -53,6 +53,9 @@ struct FrameVariant {
     int op = 0;        // proj_kernel: kProjMin or kProjMean
 };
 constexpr int kProjMin = 0, kProjMean = 1;  // proj_kernel's OP (VR_MODE_MINIP, VR_MODE_MEAN)
+// proj_strip's third operator, the maximum: mip_kernel's strip only, never a FrameVariant::op
+// (VF_MIP stays a family of its own and no proj_kernel<VT, kProjMax, ...> is built)
+constexpr int kProjMax = 2;
 
 // The resolved inputs of the decision, after the derived structures a launch reads were built
 // or refused (the fields: vr_debug.h).
