@@ -58,6 +58,7 @@
 #include "vr.h"
 #include "vr_modes.h"
 #include "vr_iso.h"
+#include "vr_mpr.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -280,6 +281,20 @@ class BasicOffscreenPass {
         for (int i = 0; i < 16; ++i) cam.view[i] = camera.view[i];
         for (int i = 0; i < 3; ++i) cam.position[i] = camera.position[i];
         check(vr_render_device(ctx_, &cam, &params_, out_dev, VR_OUT_RGBA8, 16, 0, 1, hip_stream));
+    }
+
+    // Extension (vr_mpr.h): a multi-planar reformat image -- a plane through the volume, thin or
+    // a slab -- of the plane's own size (plane.width * plane.height pixels of format `fmt`, a
+    // vr_out_format) into host memory; the render mode, the isovalue and the frame image stay as
+    // they are.  Only params().clear_color is read.
+    void render_mpr(const vr_mpr_plane &plane, void *out, int fmt)
+    {
+        check(vr_mpr_render(ctx_, &plane, &params_, out, fmt));
+    }
+    // Same into device memory on a HIP stream (asynchronous).
+    void render_mpr_device(const vr_mpr_plane &plane, void *out_dev, int fmt, void *hip_stream)
+    {
+        check(vr_mpr_render_device(ctx_, &plane, &params_, out_dev, fmt, hip_stream));
     }
 
     const std::vector<uint32_t> &image() const { return image_; }

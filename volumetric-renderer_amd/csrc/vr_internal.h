@@ -471,6 +471,51 @@ struct ProjArgs {
 // (variant_built), or MIP / ISO / MinIP / mean skipping without the brick ranges.
 hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipArgs &m,
                         const IsoArgs &i, hipStream_t stream);
+// ---- Multi-planar reformat (include/vr/vr_mpr.h, mpr_kernel) ----
+// MPR is no frame: it has no camera, an image size of its own and a parallel ray set, so its
+// kernel takes this argument alone (MarchParams does not grow) and is launched outside
+// launch_frame and FrameVariant.  The fields the shared pixel epilogue reads (vmin .. out_bytes)
+// carry MarchParams' names.
+struct MprArgs {
+    const void *vol;        // the base bricks (layout code `layout` of launch_mpr)
+    const float4 *tf;       // decoded TF texels, device (read through this global pointer)
+    void *out;              // H x W pixels
+    unsigned long long *counters;  // the counting kernel: rays, samples, shaded, steps, skipped
+    double origin[3], du[3], dv[3], dn[3];  // the plane's f32 vectors, widened (exact)
+    double half_w, half_h, half_n;  // 0.5 W, 0.5 H, 0.5 (nsamples - 1)
+    uint32_t nbx, nby;      // bricks per axis (x, y)
+    float fnx, fny, fnz;
+    float vmin, range, inv_range;
+    int32_t div_fast;
+    int32_t tf_n;
+    float tf_nf;
+    float smin[3], smax[3];
+    float clear[4];
+    uint32_t W, H, nsamples;
+    uint32_t tiles_x, tiles_y;  // 16 x 16-pixel tiles, one per workgroup
+    // workgroup -> tile: 1 raster, 3 the frames' XCD-interleaved 4 x 4-tile super-tiles
+    // (block_tile's order 3; supers_x, supers_total as MarchParams')
+    uint32_t tile_order, supers_x, supers_total;
+    int32_t out_format;
+    int32_t op;             // vr_mpr_op (the thin-slice kernel reads it; the slab kernels' is a template argument)
+    unsigned long long vol_bytes, out_bytes;  // bounds-checking debug builds
+};
+// mpr_kernel's OP: vr_mpr_op's three values over a slab, and the thin slice (nsamples == 1: one
+// instantiation per storage tag, the operator read at run time for its NaN rule alone)
+constexpr int kMprMax = 0, kMprMin = 1, kMprMean = 2, kMprThin = 3;
+// The tile order of an MPR launch unless VR_KNOB_TILE_ORDER asks for one (1 or 3).  Measured on
+// 1024^2 images of the 512^3 f32 volume at a pitch of one voxel (profiles/r13/mpr/c3.json, both
+// orders alternated in one process): 64-sample slabs run 9.4 % faster in super-tiles on the
+// sagittal plane (0.127 -> 0.115 ms), 1-2.4 % faster on the axial and oblique ones and 1.1-1.6 %
+// slower on the coronal one; thin slices (6-7 us a launch) are 0.3-0.9 us faster in raster order
+// on all four planes.
+constexpr uint32_t kMprTileOrder(uint32_t nsamples) { return nsamples == 1 ? 1u : 3u; }
+// The MPR kernel of a base layout (a storage type, or an 8-bit one | kQuadFlag) over a's tiles:
+// the slab kernel of a.op, the thin-slice kernel when a.nsamples == 1, or (count) the counting
+// kernel, which walks the positions, fetches nothing and writes no pixel.  *name (when not null):
+// the demangled kernel name.  hipErrorInvalidValue: no such layout or operator.
+hipError_t launch_mpr(int layout, bool count, const MprArgs &a, hipStream_t stream,
+                      std::string *name);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

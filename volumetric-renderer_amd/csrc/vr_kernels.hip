@@ -876,7 +876,8 @@ __device__ __forceinline__ bool pixel_ray(const MarchParams &P, uint32_t px, uin
 // IEEE division on 3.8e9 (x, range) pairs of that domain, 0 mismatches.  Smaller |x| give
 // |t| < 2^-60, where t * n - 0.5 rounds to -0.5 whatever t's last bit: the frame is the
 // same.  Otherwise the full IEEE division sequence.
-__device__ __forceinline__ float div_by_range(float x, const MarchParams &P)
+template <typename PT>
+__device__ __forceinline__ float div_by_range(float x, const PT &P)
 {
     if (P.div_fast) {
         const float q = x * P.inv_range;
@@ -1102,6 +1103,8 @@ __device__ __forceinline__ void shade_sample(const MarchParams &P, const char *_
 // (The ray walk itself -- position update, bounds break, slab test -- stays spelled out in each
 // of march_strip, proj_strip, iso_strip and march_pair_kernel: every shared form of it tried
 // moved the composite kernels' machine code or the range kernels' registers; CHANGELOG.)
+// div_by_range, flush_counters, blend_over_clear and store_pixel are templates on the parameter
+// struct: MarchParams for the frame kernels, MprArgs (same field names) for mpr_strip.
 
 // Row ly of this rank's share of the frame -> the frame's row gy (vr_internal.h RowShare);
 // false: below the frame.
@@ -1136,7 +1139,8 @@ __device__ __forceinline__ LanePixel strip_pixel(const MarchParams &P, uint32_t 
 }
 
 // The counting kernels' totals into vr_stats: rays, samples, shaded, steps, skipped.
-__device__ __forceinline__ void flush_counters(const MarchParams &P, uint32_t lane, bool covered,
+template <typename PT>
+__device__ __forceinline__ void flush_counters(const PT &P, uint32_t lane, bool covered,
                                                unsigned long long n_samples,
                                                unsigned long long n_shaded,
                                                unsigned long long n_steps,
@@ -1158,7 +1162,8 @@ __device__ __forceinline__ void flush_counters(const MarchParams &P, uint32_t la
 
 // volume.frag:50 + blend (offscreen_pass.cpp:715-725) of a ray's colour C and transmittance T
 // over the clear colour; an uncovered pixel has T = 1, C = 0 -> clear.
-__device__ __forceinline__ float4 blend_over_clear(const MarchParams &P, float cr, float cg,
+template <typename PT>
+__device__ __forceinline__ float4 blend_over_clear(const PT &P, float cr, float cg,
                                                    float cb, float T)
 {
     const float A = 1.0f - T;
@@ -1168,7 +1173,8 @@ __device__ __forceinline__ float4 blend_over_clear(const MarchParams &P, float c
 }
 
 // The pixel's colour into the rank's output: RGBA8 (UNORM8 store :293) or RGBA32F.
-__device__ __forceinline__ void store_pixel(const MarchParams &P, uint32_t px, uint32_t ly,
+template <typename PT>
+__device__ __forceinline__ void store_pixel(const PT &P, uint32_t px, uint32_t ly,
                                             float4 o)
 {
     const size_t idx = (size_t)ly * P.W + px;
@@ -1754,6 +1760,149 @@ __global__ __launch_bounds__(kThreadsPerTile) void proj_kernel(const MarchParams
     const long long wg_start = wall_clock64();
     proj_strip<VT, OP, COUNT, SKIP, K>(P, M, tile_x, tile_y, (uint32_t)tid >> 6, (uint32_t)tid & 63u);
     write_tile_cost(P, tile_x, tile_y, wg_start);
+}
+
+// ---- multi-planar reformat (include/vr/vr_mpr.h) -----------------------------------------------
+// A plane through the volume, thin or thickened into a slab of nsamples positions along its
+// normal: a parallel, short ray set that starts on the plane instead of at the camera.  One pixel
+// per lane, 16 x 16-pixel tiles (thin slices in raster order, slabs in the frames' XCD-interleaved
+// super-tiles: kMprTileOrder), a wavefront the 16 x 4 strip of strip_pixel.
+// Sample s of pixel (px, py) is at
+//     q = (float)(origin + cx du + cy dv + t dn),   cx = px + 0.5 - W / 2, cy = py + 0.5 - H / 2,
+//                                                   t = s - (nsamples - 1) / 2
+// left to right in double, rounded once (contraction is off, and each product is exact anyway):
+// the prefix origin + cx du + cy dv is the pixel's own, and no position depends on the one
+// before it, so the loads of up to K = 4 samples are issued before any is filtered, as
+// proj_strip's, with its MipRaw and the composite's Cell8::tri.  The trip count is uniform, so a
+// step no lane of the wavefront samples (an overhanging image, the slice box) loads nothing.
+// Unlike a march a position outside the cube is passed over, not the end of the ray.
+// OP = kMprMax / kMprMin / kMprMean: proj_strip's operators (NaN rules included); the mean adds
+// in s order into the one running sum whatever K is.  kMprThin: nsamples == 1, no loop; the
+// three operators then differ for a NaN sample only, so one instantiation per storage tag reads
+// A.op at run time and performs that operator's own single operation.
+// COUNT: walks the positions and fills vr_stats (rays = pixels with a step; shaded and skipped
+// 0); it fetches nothing and writes no pixel, so one instantiation serves every layout.
+template <typename VT, int OP, bool COUNT>
+__device__ __forceinline__ void mpr_strip(const MprArgs &A, uint32_t tile_x, uint32_t tile_y,
+                                          uint32_t wave, uint32_t lane)
+{
+    static_assert(OP == kMprMax || OP == kMprMin || OP == kMprMean || OP == kMprThin, "vr_mpr_op or thin");
+    constexpr bool MEAN = OP == kMprMean, MAX = OP == kMprMax, THIN = OP == kMprThin;
+    constexpr int K = THIN ? 1 : 4;
+    const uint32_t px = tile_x * kTile + (lane & 15u);
+    const uint32_t py = tile_y * kTile + wave * 4u + (lane >> 4);
+    const bool active = px < A.W && py < A.H;
+
+    const double cx = (double)px + 0.5 - A.half_w, cy = (double)py + 0.5 - A.half_h;
+    double b[3];  // the pixel's prefix of the position sum
+#pragma unroll
+    for (int a = 0; a < 3; ++a) b[a] = A.origin[a] + cx * A.du[a] + cy * A.dv[a];
+
+    // slab kernels: the running maximum, minimum or sum; thin: the one sample
+    float m = MEAN ? 0.0f : MAX ? -INFINITY : INFINITY;
+    int n = 0;  // in-slab samples so far
+    unsigned long long n_steps = 0;
+    const char *__restrict__ vol = static_cast<const char *>(A.vol);
+    const uint32_t ns = THIN ? 1u : A.nsamples;
+
+    struct Stage {
+        MipRaw<VT> r;
+        float ax, ay, az;
+        bool slab, issued;
+    };
+    for (uint32_t it = 0; it < ns; it += K) {
+        Stage S[K];
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const double t = (double)(it + (uint32_t)s) - A.half_n;
+            const float q0 = (float)(b[0] + t * A.dn[0]);
+            const float q1 = (float)(b[1] + t * A.dn[1]);
+            const float q2 = (float)(b[2] + t * A.dn[2]);
+            // the march's bounds test: a position outside is no step
+            const bool step = active && it + (uint32_t)s < ns &&
+                              !(q0 > 1.0f || q1 > 1.0f || q2 > 1.0f || q0 < 0.0f || q1 < 0.0f ||
+                                q2 < 0.0f);
+            if (COUNT && step) ++n_steps;
+            // the march's strict slab test
+            const bool slab = step && q0 < A.smax[0] && q1 < A.smax[1] && q2 < A.smax[2] &&
+                              q0 > A.smin[0] && q1 > A.smin[1] && q2 > A.smin[2];
+            S[s].slab = slab;
+            if constexpr (COUNT) {
+                S[s].issued = false;
+            } else {
+                int i, j, kk;
+                texel_coord(q0, A.fnx, i, S[s].ax);
+                texel_coord(q1, A.fny, j, S[s].ay);
+                texel_coord(q2, A.fnz, kk, S[s].az);
+                // in the cube: i in [-1, n - 1], padded index in [1, n + 1] (vr_internal.h bricks_for)
+                size_t ce = slab ? cell_offset<VT>(i + kPad, j + kPad, kk + kPad, A.nbx, A.nby)
+                                 : (size_t)0;
+                if (VR_OOB(2, ce * kElemBytes<VT>, A.vol_bytes)) ce = 0;
+                S[s].issued = __any(slab);
+                if (S[s].issued) S[s].r.issue(vol, ce);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {  // in s order: the mean's additions are ordered
+            if constexpr (COUNT) {
+                if (S[s].slab) ++n;
+            } else if (S[s].issued) {
+                Cell8<VT> c;
+                S[s].r.decode(c);
+                const float d = c.tri(S[s].ax, S[s].ay, S[s].az);
+                if (S[s].slab) {
+                    ++n;
+                    if constexpr (THIN)
+                        m = A.op == kMprMax   ? fmaxf(-INFINITY, d)
+                            : A.op == kMprMin ? fminf(INFINITY, d)
+                                              : (0.0f + d) / 1.0f;
+                    else if constexpr (MEAN)
+                        m = m + d;
+                    else if constexpr (MAX)
+                        m = fmaxf(m, d);  // a NaN sample leaves m
+                    else
+                        m = fminf(m, d);
+                }
+            }
+        }
+    }
+
+    if constexpr (COUNT) {
+        flush_counters(A, lane, n_steps > 0, (unsigned long long)n, 0, n_steps, 0);
+        return;
+    }
+    if (!active) return;
+    // one composite step from T = 1 (volume.frag:42-45), then the blend over the clear colour
+    float T = 1.0f, cr = 0.0f, cg = 0.0f, cb = 0.0f;
+    if (n > 0) {
+        const float v = MEAN ? m / (float)n : m;  // (the correctly rounded quotient: Makefile)
+        // A pixel whose samples are all NaN keeps the operator's start, -+INFINITY, and x is then
+        // infinite: the IEEE quotient by the (positive, div_fast) range is x itself, where
+        // div_by_range's residual correction would give inf - inf = NaN (texel 0 for +inf too).
+        const float x = v - A.vmin;
+        const float tt = A.div_fast && fabsf(x) == INFINITY ? x : div_by_range(x, A);
+        const float4 s = tf_lookup(A.tf, A.tf_n, A.tf_nf, tt);
+        cr = (s.x * s.w) * 1.0f;
+        cg = (s.y * s.w) * 1.0f;
+        cb = (s.z * s.w) * 1.0f;
+        T = 1.0f * (1.0f - s.w);
+    }
+    store_pixel(A, px, py, blend_over_clear(A, cr, cg, cb, T));
+}
+
+template <typename VT, int OP, bool COUNT>
+__global__ __launch_bounds__(kTile * kTile) void mpr_kernel(const MprArgs A)
+{
+    const uint32_t tid = threadIdx.x, b = blockIdx.x;
+    uint32_t tile_x = b % A.tiles_x, tile_y = b / A.tiles_x;
+    if (A.tile_order == 3) {  // block_tile's order 3: workgroups b and b + 8 share an XCD
+        const uint32_t k = b >> 3, w = k & (kSuper * kSuper - 1);
+        const uint32_t s = (b & 7u) + 8u * (k >> (2 * kSuperShift));
+        tile_x = (s % A.supers_x) * kSuper + (w & (kSuper - 1));
+        tile_y = (s / A.supers_x) * kSuper + (w >> kSuperShift);
+        if (!(s < A.supers_total && tile_x < A.tiles_x && tile_y < A.tiles_y)) return;  // grid padding
+    }
+    mpr_strip<VT, OP, COUNT>(A, tile_x, tile_y, tid >> 6, tid & 63u);
 }
 
 // ---- first-hit isosurface (include/vr/vr_iso.h) ----------------------------------------------
@@ -2821,6 +2970,57 @@ hipError_t launch_frame(const FrameVariant &v, const MarchParams &p, const MipAr
                              : p.tile_order >= 3 ? ((p.supers_total + 7) / 8) * 8 * kSuper * kSuper
                                                  : p.tiles_x * p.tiles_y;
     fn(nblocks, p, m, iso, stream);
+    return hipGetLastError();
+}
+
+namespace {
+template <typename VT>
+void launch_mpr_tag(const MprArgs &a, uint32_t nblocks, hipStream_t stream)
+{
+    const dim3 grid(nblocks), block(kTile * kTile);
+    if (a.nsamples == 1)
+        hipLaunchKernelGGL((mpr_kernel<VT, kMprThin, false>), grid, block, 0, stream, a);
+    else if (a.op == kMprMax)
+        hipLaunchKernelGGL((mpr_kernel<VT, kMprMax, false>), grid, block, 0, stream, a);
+    else if (a.op == kMprMin)
+        hipLaunchKernelGGL((mpr_kernel<VT, kMprMin, false>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL((mpr_kernel<VT, kMprMean, false>), grid, block, 0, stream, a);
+}
+}  // namespace
+
+hipError_t launch_mpr(int layout, bool count, const MprArgs &a, hipStream_t stream, std::string *name)
+{
+    const int tag = layout >= ST_U8 && layout <= ST_F32 ? layout
+                    : layout == (ST_U8 | kQuadFlag)     ? (int)TAG_QUAD_U8
+                    : layout == (ST_I8 | kQuadFlag)     ? (int)TAG_QUAD_I8
+                                                        : -1;
+    if (tag < 0 || a.op < kMprMax || a.op > kMprMean || a.nsamples == 0) return hipErrorInvalidValue;
+    if (name)
+        *name = std::string("void vr::(anonymous namespace)::mpr_kernel<") + kTagNames[count ? (int)TAG_F32 : tag] +
+                ", " + std::to_string(count ? kMprMax : a.nsamples == 1 ? kMprThin : a.op) +
+                (count ? ", true" : ", false") + ">(vr::MprArgs)";
+    const unsigned long long tiles = (unsigned long long)a.tiles_x * a.tiles_y;
+    if (tiles == 0) return hipSuccess;
+    if (tiles >= 1ull << 31) return hipErrorInvalidValue;
+    // order 3: whole super-tiles, dealt over the 8 XCDs (launch_frame's grid)
+    const unsigned long long padded = ((a.supers_total + 7ull) / 8) * 8 * kSuper * kSuper;
+    if (a.tile_order == 3 && padded >= 1ull << 31) return hipErrorInvalidValue;
+    const uint32_t nblocks = a.tile_order == 3 ? (uint32_t)padded : (uint32_t)tiles;
+    if (count) {
+        hipLaunchKernelGGL((mpr_kernel<float, kMprMax, true>), dim3(nblocks), dim3(kTile * kTile), 0,
+                           stream, a);
+        return hipGetLastError();
+    }
+    switch (tag) {
+        case TAG_U8: launch_mpr_tag<uint8_t>(a, nblocks, stream); break;
+        case TAG_I8: launch_mpr_tag<int8_t>(a, nblocks, stream); break;
+        case TAG_U16: launch_mpr_tag<uint16_t>(a, nblocks, stream); break;
+        case TAG_I16: launch_mpr_tag<int16_t>(a, nblocks, stream); break;
+        case TAG_F32: launch_mpr_tag<float>(a, nblocks, stream); break;
+        case TAG_QUAD_U8: launch_mpr_tag<Quad8<uint8_t>>(a, nblocks, stream); break;
+        default: launch_mpr_tag<Quad8<int8_t>>(a, nblocks, stream); break;
+    }
     return hipGetLastError();
 }
 

@@ -13,6 +13,11 @@
 //                                        mean-intensity projection, include/vr/vr_modes.h;
 //                                        iso: first-hit isosurface, include/vr/vr_iso.h)
 //          [--iso V]   (the isosurface's density, in the volume's units; default 0)
+//          [--mpr AXIS:POSITION[:NSAMPLES:SPACING:OP]]   (AXIS axial|coronal|sagittal, OP
+//                                        max|min|mean: write the multi-planar reformat image
+//                                        of include/vr/vr_mpr.h at --size -- the plane at
+//                                        POSITION in [0,1] along the axis, thin or a slab of
+//                                        NSAMPLES samples SPACING apart -- instead of the 3D frame)
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +33,8 @@ int main(int argc, char **argv)
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <file.nhdr|synthetic:N> <out.ppm> [--size WxH] [--radius R] "
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
-                             "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V]\n",
+                             "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V] "
+                             "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]]\n",
                      argv[0]);
         return 2;
     }
@@ -37,7 +43,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default", mode = "composite";
+    std::string tfname = "default", mode = "composite", mpr;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -50,6 +56,7 @@ int main(int argc, char **argv)
         else if (a == "--ert" && i + 1 < argc) ert = std::strtof(argv[++i], nullptr);
         else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
         else if (a == "--iso" && i + 1 < argc) iso = std::strtof(argv[++i], nullptr);
+        else if (a == "--mpr" && i + 1 < argc) mpr = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -60,6 +67,31 @@ int main(int argc, char **argv)
     if (mode != "composite" && mode != "mip" && mode != "iso" && mode != "minip" && mode != "mean") {
         std::fprintf(stderr, "unknown mode %s\n", mode.c_str());
         return 2;
+    }
+    // --mpr AXIS:POSITION[:NSAMPLES:SPACING:OP]
+    vr_mpr_plane plane{};
+    if (!mpr.empty()) {
+        std::vector<std::string> f;
+        for (size_t b = 0;;) {
+            const size_t e = mpr.find(':', b);
+            f.push_back(mpr.substr(b, e == std::string::npos ? e : e - b));
+            if (e == std::string::npos) break;
+            b = e + 1;
+        }
+        const int axis = f[0] == "sagittal" ? 0 : f[0] == "coronal" ? 1 : f[0] == "axial" ? 2 : -1;
+        const int op = f.size() == 5 ? (f[4] == "max" ? VR_MPR_MAX : f[4] == "min" ? VR_MPR_MIN
+                                        : f[4] == "mean" ? VR_MPR_MEAN : -1)
+                                     : VR_MPR_MAX;
+        if (axis < 0 || (f.size() != 2 && f.size() != 5) || op < 0) {
+            std::fprintf(stderr, "bad --mpr %s (AXIS:POSITION[:NSAMPLES:SPACING:OP])\n", mpr.c_str());
+            return 2;
+        }
+        const uint32_t ns = f.size() == 5 ? (uint32_t)std::strtoul(f[2].c_str(), nullptr, 10) : 1u;
+        const float spacing = f.size() == 5 ? std::strtof(f[3].c_str(), nullptr) : 0.0f;
+        if (vr_mpr_axis_plane(axis, std::strtof(f[1].c_str(), nullptr), W, H, ns, spacing, op, &plane) != VR_OK) {
+            std::fprintf(stderr, "bad --mpr %s: %s\n", mpr.c_str(), vr_last_error(nullptr));
+            return 2;
+        }
     }
     try {
         Vol::Rendering::Hip::OffscreenPass pass = mask ? Vol::Rendering::Hip::OffscreenPass(
@@ -111,10 +143,16 @@ int main(int argc, char **argv)
         pass.params().ert_eps = ert;
 
         auto t0 = std::chrono::steady_clock::now();
-        for (int f = 0; f < frames; ++f) pass.render(cam);
+        std::vector<uint32_t> mpr_img(mpr.empty() ? 0 : (size_t)W * H);
+        for (int f = 0; f < frames; ++f) {
+            if (mpr.empty())
+                pass.render(cam);
+            else
+                pass.render_mpr(plane, mpr_img.data(), VR_OUT_RGBA8);
+        }
         auto t1 = std::chrono::steady_clock::now();
         const double ms = std::chrono::duration<double, std::milli>(t1 - t0).count() / frames;
-        const std::vector<uint32_t> &img = pass.image();
+        const std::vector<uint32_t> &img = mpr.empty() ? pass.image() : mpr_img;
         FILE *fp = std::fopen(out.c_str(), "wb");
         if (!fp) throw std::runtime_error("cannot write " + out);
         std::fprintf(fp, "P6\n%u %u\n255\n", W, H);

@@ -91,6 +91,12 @@ class vr_variant_facts(C.Structure):  # vr_debug.h
         "pair", "mip_inflight")]
 
 
+class vr_mpr_plane(C.Structure):  # vr_mpr.h
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3),
+                ("dn", C.c_float * 3), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("nsamples", C.c_uint32), ("op", C.c_int32)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -137,6 +143,11 @@ MODE_ISO = 3  # (2 is unassigned and refused)
 MODE_MINIP, MODE_MEAN = 4, 6  # minimum- and mean-intensity projection (5 is unassigned and refused)
 # include/vr/vr_iso.h: the isovalue of VR_MODE_ISO (context state)
 ISO_SYMBOLS = ["vr_set_isovalue", "vr_get_isovalue"]
+# include/vr/vr_mpr.h: multi-planar reformat (its own entry points, no render mode) and enum vr_mpr_op
+MPR_SYMBOLS = ["vr_mpr_render", "vr_mpr_render_device", "vr_mpr_count_work", "vr_mpr_axis_plane"]
+OP_MAX, OP_MIN, OP_MEAN = 0, 1, 2
+MPR_MAX_SAMPLES = 4096
+AXIS_SAGITTAL, AXIS_CORONAL, AXIS_AXIAL = 0, 1, 2
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -227,6 +238,11 @@ def lib() -> C.CDLL:
         "vr_get_render_mode": (i32, [vp, C.POINTER(i32)]),
         "vr_set_isovalue": (i32, [vp, C.c_float]),
         "vr_get_isovalue": (i32, [vp, C.POINTER(C.c_float)]),
+        "vr_mpr_render": (i32, [vp, C.POINTER(vr_mpr_plane), C.POINTER(vr_params), vp, i32]),
+        "vr_mpr_render_device": (i32, [vp, C.POINTER(vr_mpr_plane), C.POINTER(vr_params), vp, i32, vp]),
+        "vr_mpr_count_work": (i32, [vp, C.POINTER(vr_mpr_plane), C.POINTER(vr_params),
+                                    C.POINTER(vr_stats)]),
+        "vr_mpr_axis_plane": (i32, [i32, f32, u32, u32, u32, f32, i32, C.POINTER(vr_mpr_plane)]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
@@ -264,6 +280,29 @@ def lib() -> C.CDLL:
                            f"{ABI_VERSION}: rebuild it")
     _LIB = L
     return L
+
+
+def mpr_plane(origin, du, dv, dn, width: int, height: int, nsamples: int = 1,
+              op: int = OP_MAX) -> vr_mpr_plane:
+    """A vr_mpr_plane from texture-space vectors (rounded to f32 as the struct holds them)."""
+    pl = vr_mpr_plane()
+    for name, v in (("origin", origin), ("du", du), ("dv", dv), ("dn", dn)):
+        for a in range(3):
+            getattr(pl, name)[a] = float(v[a])
+    pl.width, pl.height, pl.nsamples, pl.op = int(width), int(height), int(nsamples), int(op)
+    return pl
+
+
+def axis_plane(axis: int, position: float, width: int, height: int, nsamples: int = 1,
+               spacing: float = 0.0, op: int = OP_MAX) -> vr_mpr_plane:
+    """vr_mpr_axis_plane: the axis-aligned plane (AXIS_SAGITTAL / AXIS_CORONAL / AXIS_AXIAL) at
+    `position` showing the whole cross-section; ValueError where the C function refuses."""
+    pl = vr_mpr_plane()
+    rc = lib().vr_mpr_axis_plane(int(axis), float(position), int(width), int(height), int(nsamples),
+                                 float(spacing), int(op), C.byref(pl))
+    if rc != 0:
+        raise ValueError(f"vr_mpr_axis_plane failed ({rc}): {lib().vr_last_error(None).decode()}")
+    return pl
 
 
 def default_params(**overrides) -> vr_params:
@@ -575,6 +614,32 @@ class OffscreenPass:
         self._check(lib().vr_render(self._ctx, C.byref(cam), C.byref(p), out.ctypes.data, out_format),
                     "render")
         return out
+
+    # -- multi-planar reformat (vr_mpr.h): its own image size, no camera, no render mode --
+    def render_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None,
+                   out_format: int = OUT_RGBA32F) -> np.ndarray:
+        """vr_mpr_render: the plane's (height, width, 4) image, float32 or uint8."""
+        p = params if params is not None else default_params()
+        out = np.empty((plane.height, plane.width, 4),
+                       dtype=np.float32 if out_format == OUT_RGBA32F else np.uint8)
+        self._check(lib().vr_mpr_render(self._ctx, C.byref(plane), C.byref(p), out.ctypes.data,
+                                        out_format), "render_mpr")
+        return out
+
+    def render_mpr_device(self, plane: vr_mpr_plane, params: Optional[vr_params], out_ptr: int,
+                          out_format: int = OUT_RGBA8, stream: int = 0):
+        p = params if params is not None else default_params()
+        self._check(lib().vr_mpr_render_device(self._ctx, C.byref(plane), C.byref(p),
+                                               C.c_void_p(out_ptr), out_format,
+                                               C.c_void_p(stream or None)), "render_mpr_device")
+
+    def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
+        p = params if params is not None else default_params()
+        st = vr_stats()
+        self._check(lib().vr_mpr_count_work(self._ctx, C.byref(plane), C.byref(p), C.byref(st)),
+                    "count_work_mpr")
+        return dict(rays=st.rays, samples=st.samples, shaded_samples=st.shaded_samples,
+                    steps=st.steps, skipped_samples=st.skipped_samples)
 
     def render_device(self, camera, params, out_ptr: int, out_format: int = OUT_RGBA8,
                       row_block: int = 16, rank: int = 0, nranks: int = 1, stream: int = 0):
