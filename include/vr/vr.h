@@ -340,9 +340,11 @@ enum vr_derived {
     VR_DERIVED_PLAIN_COPY = 3,     /* plain 15^3-cell copy        */
     VR_DERIVED_STENCIL_COPY = 4,   /* stencil copy                */
     VR_DERIVED_SKIP = 5,           /* skip-empty classification   */
-    VR_DERIVED_YMAJOR_COPY = 6     /* y-major copy (dense-row views along y): counted only when
+    VR_DERIVED_YMAJOR_COPY = 6,    /* y-major copy (dense-row views along y): counted only when
                                       forced (vr_debug.h knob); left to the policy it is built
                                       into spare budget alone and its absence is no downgrade */
+    VR_DERIVED_YMAJOR_FIELD = 7    /* y-major binary16 difference field, read with the y-major
+                                      copy in place of the difference field: the same rules   */
 };
 #define VR_MEMORY_BUDGET_UNLIMITED (~(uint64_t)0)
 #define VR_MEMORY_BUDGET_DEFAULT (~(uint64_t)0 - 1)

@@ -44,8 +44,12 @@ enum vr_knob {
                                copy (y-pair elements, y slowest in a brick; auto: dense-row
                                views along y of volumes beyond 256 MiB of bricks), whenever the
                                launch allows it (2, the retired z-pair sparse copy: EINVAL) */
-    VR_KNOB_MIP_INFLIGHT = 10 /* VR_MODE_MIP and VR_MODE_ISO (vr_modes.h): samples of a ray whose
+    VR_KNOB_MIP_INFLIGHT = 10, /* VR_MODE_MIP and VR_MODE_ISO (vr_modes.h): samples of a ray whose
                                loads are in flight together: 0 auto, 1, 2 or 4 (same bytes) */
+    VR_KNOB_FIELD_ORDER = 11  /* shaded frames that read the y-major copy: -1 auto (the y-major
+                               binary16 field where the policy chose the copy), 0 the z-major
+                               difference field only, 1 the y-major field on every frame that
+                               reads the copy, at any volume size (same bytes)              */
 };
 
 /* Per-device timing of a context (ABI 7), so that a multi-GPU frame that runs slow names its
@@ -128,6 +132,8 @@ const char *vr_debug_last_kernel_name(const vr_ctx *ctx);
  * vr_memory_info.derived_bytes like every derived structure; the ABI 9 struct has no field of
  * its own for it. */
 uint64_t vr_debug_ymajor_copy_bytes(const vr_ctx *ctx);
+/* Device bytes of the y-major binary16 difference field (VR_DERIVED_YMAJOR_FIELD; 0: absent). */
+uint64_t vr_debug_ymajor_field_bytes(const vr_ctx *ctx);
 
 #ifdef __cplusplus
 }

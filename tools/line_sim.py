@@ -323,16 +323,43 @@ def zpair_geom(BX, BY, BZ, vb=4):
     return fn
 
 
-def ypair_geom(BX=8, BY=8, BZ=8, vb=4):
+def brick_slot_of(order):
+    """Slot of brick (bx, by, bz) in a cubic nb-brick grid: "xyz" x fastest, then y, then z
+    (brick_slot); "xzy" x, then z, then y (ymajor_slot, the y-major structures since round 14)."""
+    if order == "xyz":
+        return lambda bx, by, bz, nb: (bz * nb + by) * nb + bx
+    if order == "xzy":
+        return lambda bx, by, bz, nb: (by * nb + bz) * nb + bx
+    raise ValueError(order)
+
+
+def ypair_geom(BX=8, BY=8, BZ=8, vb=4, brick_order="xyz"):
     """f32 y-pairs in the y-major copy (vr_internal.h F32Y): elements x + EX (z + EZ y) in a
-    brick, the bricks in the same order; a sample = 2 x 16-B loads at e and e + EX (rows z, z + 1)."""
+    brick, the bricks in `brick_order` ("xyz": round 9's; "xzy": round 14's, which moves no line
+    and only their places); a sample = 2 x 16-B loads at e and e + EX (rows z, z + 1)."""
     EX, EY, EZ = BX + 1, BY + 1, BZ + 1
+    slot = brick_slot_of(brick_order)
 
     def fn(i, j, k, nb):
         pi, pj, pk = i + 2, j + 2, k + 2
-        b = ((pk // BZ) * nb + (pj // BY)) * nb + (pi // BX)
+        b = slot(pi // BX, pj // BY, pk // BZ, nb)
         base = (b * EX * EY * EZ + ((pj % BY) * EZ + (pk % BZ)) * EX + (pi % BX)) * 2 * vb
         return [(base, 4 * vb), (base + EX * 2 * vb, 4 * vb)]
+    return fn
+
+
+def field_geom(major="z", brick_order="xyz", B=8):
+    """The binary16 difference field: 24-B elements on the 8^3 brick grid, z-major in a brick
+    (x + 9 (y + 9 z), shared with the z-pair bricks) or y-major (x + 9 (z + 9 y), the y-major
+    field); a shaded sample = 3 x 16-B loads, the 48 B of elements x and x + 1."""
+    E = B + 1
+    slot = brick_slot_of(brick_order)
+
+    def fn(i, j, k, nb):
+        pi, pj, pk = i + 2, j + 2, k + 2
+        lo, hi = (pj % B, pk % B) if major == "z" else (pk % B, pj % B)
+        base = (slot(pi // B, pj // B, pk // B, nb) * E ** 3 + (hi * E + lo) * E + (pi % B)) * 24
+        return [(base, 16), (base + 16, 16), (base + 32, 16)]
     return fn
 
 
@@ -350,7 +377,7 @@ def frame_lines(view_name, layout, n=512, W=1920, H=1080, line=128, rows_per_pas
           else synth.camera(view_name)).to_vr_camera()
     view, pos = list(vc.view), list(vc.position)
     nb = (n + 3) // 4 + 1
-    top = (nb ** 3) * 9 ** 3 * 8 // line + 2
+    top = (nb ** 3) * 9 ** 3 * 24 // line + 2  # (24-B elements: the field layouts)
     seen = np.zeros(top, dtype=bool)
     samples = 0
     for y0 in range(0, H, rows_per_pass):
@@ -417,6 +444,17 @@ if __name__ == "__main__":
                 r = frame_lines(vname, fn, n)
                 print(f"{vname:6s} {lname:12s} samples {r['samples'] / 1e6:7.1f} M  distinct lines "
                       f"{r['lines'] / 1e6:6.2f} M = {r['bytes'] / 1e9:.3f} GB", flush=True)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "field":
+        # field [n]: distinct line bytes of the difference field if every sample of the fill
+        # view were shaded, z-major against y-major elements, either brick order
+        n = int(sys.argv[2]) if len(sys.argv) > 2 else 512
+        for lname, fn in (("z-major, bricks xyz", field_geom("z", "xyz")),
+                          ("y-major, bricks xyz", field_geom("y", "xyz")),
+                          ("y-major, bricks xzy", field_geom("y", "xzy"))):
+            r = frame_lines("fill", fn, n)
+            print(f"fill   field {lname:20s} samples {r['samples'] / 1e6:7.1f} M  distinct lines "
+                  f"{r['lines'] / 1e6:6.2f} M = {r['bytes'] / 1e9:.3f} GB", flush=True)
         sys.exit(0)
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 512
     cams = {"fill": synth.camera("fill"), "fill_oblique": synth.camera("fill_oblique"),

@@ -38,6 +38,15 @@ def summarise(d):
         out["l1_hit_rate"] = 1 - m["TCP_TCC_READ_REQ_sum"] / m["TCP_TOTAL_CACHE_ACCESSES_sum"]
     if m.get("TD_TD_BUSY_sum"):
         out["td_tc_stall_over_td_busy"] = m["TD_TC_STALL_sum"] / m["TD_TD_BUSY_sum"]
+    # address translation and the L1's read-request latency (tools/pmc_sets_tlb.txt)
+    if "TCP_UTCL1_TRANSLATION_MISS_sum" in m:
+        out["utcl1_translation_miss"] = m["TCP_UTCL1_TRANSLATION_MISS_sum"]
+        if m.get("TCP_UTCL1_REQUEST_sum"):
+            out["utcl1_miss_per_request"] = (m["TCP_UTCL1_TRANSLATION_MISS_sum"] /
+                                             m["TCP_UTCL1_REQUEST_sum"])
+    if "TCP_TCC_READ_REQ_LATENCY_sum" in m and m.get("TCP_TCC_READ_REQ_sum"):
+        out["tcc_read_latency_cycles_per_request"] = (m["TCP_TCC_READ_REQ_LATENCY_sum"] /
+                                                      m["TCP_TCC_READ_REQ_sum"])
     return out
 
 

@@ -85,6 +85,12 @@ struct vr_ctx {
     bool grad_valid = false;
     uint64_t grad_used = 0;  // frame_no of the latest frame that read it
     bool grad_half = false;      // the field's precision (vr_params.exact_gradient == 0: binary16)
+    // the y-major binary16 field (vr_internal.h F32Y; launch_grad_field ymajor): what a shaded
+    // frame on the y-major copy reads in place of `grad`; opportunistic as that copy (ensure_yfield)
+    float *ygrad = nullptr;  // stream-ordered allocation (hipMallocAsync)
+    size_t ygrad_bytes = 0;
+    bool ygrad_valid = false;
+    int ygrad_scale_log2 = 0;
     int grad_scale_log2 = 0;     // and its scale (field_scale_log2 of the data's own range)
     // f32 storage: the stored voxels' min and max, zero border included (measured on the bricks
     // at upload): the binary16 field's scale comes from these, never from the caller's
@@ -153,7 +159,7 @@ struct vr_ctx {
     // product path never reads the process environment
     struct Knobs {
         int pipeline = -1, pair = -1, pair_lanes = 0, grad_field = -1, u8_layout = -1,
-            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0;
+            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0, field_order = -1;
     } knobs;
     // multi-device context (vr_create_mask): one member context per device of the mask, the
     // volume/TF/slicing replicated on each, frames rendered across them by `group`
@@ -437,7 +443,7 @@ void free_derived(vr_ctx *c);
 int set_bricks(vr_ctx *c, int storage, uint32_t nx, uint32_t ny, uint32_t nz, void **out)
 {
     c->range_valid = c->dist_valid = false;  // the bricks are about to be rewritten
-    c->grad_valid = false;
+    c->grad_valid = c->ygrad_valid = false;
     for (auto &a : c->alt) a.valid = a.failed = false;
     const size_t bytes = (size_t)bricks_for(nx, 0, storage) * bricks_for(ny, 1, storage) *
                          bricks_for(nz, 2, storage) * brick_elems(storage) * element_size(storage);
@@ -711,6 +717,7 @@ int build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
     P.nz = c->nz;
     P.nbx = bricks_for(c->nx, 0, c->layout);
     P.nby = bricks_for(c->ny, 1, c->layout);
+    P.nbz = bricks_for(c->nz, 2, c->layout);
     P.fnx = (float)c->nx;
     P.fny = (float)c->ny;
     P.fnz = (float)c->nz;
@@ -789,7 +796,7 @@ int record_build(vr_ctx *c, hipStream_t s)
 constexpr size_t kSkipBytesPerBrick = sizeof(float2) + 2;  // range + distance field + scratch
 size_t derived_bytes(const vr_ctx *c)
 {
-    size_t b = c->grad ? c->grad_bytes : 0;
+    size_t b = (c->grad ? c->grad_bytes : 0) + (c->ygrad ? c->ygrad_bytes : 0);
     for (const auto &a : c->alt)
         if (a.bricks) b += a.bytes + kBrickSlackBytes;
     return b + c->nbricks_alloc * kSkipBytesPerBrick;
@@ -890,7 +897,7 @@ constexpr int kYMajorAlt = 3;  // alt_index of the y-major copy
 // `replaced` bytes of the same structure) fit the budget; never the copy `keep_alt` (alt index,
 // or -1) the frame reads, nor the field when `keep_field`.  Returns VR_OK with *fits.
 int make_room(vr_ctx *c, size_t extra, size_t replaced, int keep_alt, bool keep_field, hipStream_t s,
-              bool *fits)
+              bool *fits, bool keep_yfield = false)
 {
     *fits = budget_allows(c, extra, replaced);
     while (!*fits) {
@@ -906,10 +913,17 @@ int make_room(vr_ctx *c, size_t extra, size_t replaced, int keep_alt, bool keep_
                 oldest = c->alt[i].used;
             }
         // the y-major copy goes first, whatever its age: its views lose 5-6 per cent without it
-        // (DESIGN.md §8), every other structure's views more (want_alt)
+        // (DESIGN.md §8), every other structure's views more (want_alt); and before it the
+        // y-major field, which only that copy's frames read and the z-major field stands in for
         if (keep_alt != kYMajorAlt && c->alt[kYMajorAlt].bricks) pick = kYMajorAlt;
+        if (c->ygrad && !keep_yfield) pick = -3;
         if (pick == -2) return VR_OK;  // nothing left to evict: does not fit
-        if (pick == -1) {
+        if (pick == -3) {
+            if (int rc = release_async(c, c->ygrad, s)) return rc;
+            c->ygrad = nullptr;
+            c->ygrad_bytes = 0;
+            c->ygrad_valid = false;
+        } else if (pick == -1) {
             if (int rc = release_async(c, c->grad, s)) return rc;
             c->grad = nullptr;
             c->grad_bytes = 0;
@@ -930,6 +944,10 @@ void free_derived(vr_ctx *c)
     c->grad = nullptr;
     c->grad_bytes = 0;
     c->grad_valid = false;
+    if (c->ygrad) (void)hipFreeAsync(c->ygrad, nullptr);
+    c->ygrad = nullptr;
+    c->ygrad_bytes = 0;
+    c->ygrad_valid = false;
     for (auto &a : c->alt) {
         if (a.bricks) (void)hipFreeAsync(a.bricks, nullptr);
         a = vr_ctx::AltCopy();
@@ -1065,7 +1083,7 @@ bool ensure_grad(vr_ctx *c, MarchParams &P, hipStream_t s, bool half, bool *refu
     }
     if (!c->grad_valid) {
         if (launch_grad_field(static_cast<const float *>(c->bricks), c->grad, c->nx, c->ny, c->nz,
-                              half, k, s) != hipSuccess)
+                              half, k, false, s) != hipSuccess)
             return built;
         built = true;
         ++c->n_builds;
@@ -1110,7 +1128,8 @@ int ensure_derived(vr_ctx *c, const vr_params *p, MarchParams &P, hipStream_t s,
     }
     // (a precision switch rebuilds a field that was valid on entry: ask ensure_grad, not the flag)
     bool g_refused = false;
-    const bool g_built = p->shading && ensure_grad(c, P, s, p->exact_gradient == 0, &g_refused);
+    const bool g_built = p->shading && !P.grad_ymajor &&
+                         ensure_grad(c, P, s, p->exact_gradient == 0, &g_refused);
     if (g_refused) *refused = VR_DERIVED_FIELD;
     const bool built = (!r0 && c->range_valid) || (!d0 && c->dist_valid) || g_built;
     if (built) return record_build(c, s);
@@ -1248,8 +1267,9 @@ IsoArgs iso_args(const vr_ctx *c, const vr_params *p, const MipArgs &M)
 // orbit) read the y-major copy (kYMajorFlag; vr_internal.h F32Y): in the z-pair bricks each of
 // their 2.56-voxel steps reads rows y and y + 1 of every z-layer, nearly every line of the
 // volume; y-major, a step passes whole y-layers by (0.62x the distinct lines per frame,
-// tools/line_sim.py frame).  It is the one copy read together with the difference field, which
-// stays z-major (shaded frames: the binary16 field only).  Its kernels exist in the pipelined
+// tools/line_sim.py frame).  It is the one copy read together with a difference field (shaded
+// frames: binary16 only) -- the y-major one in its own brick and element order where the frame
+// got it (yfield_wanted, ensure_yfield), else the shared z-major one.  Its kernels exist in the pipelined
 // single-lane form alone, so: no lane groups, skip-empty or counting, the TF within the LDS
 // copy.  Auto, only with every launch-policy knob at its default and only for bricks beyond the
 // 256 MiB Infinity Cache -- a smaller volume is cache-resident and has no line traffic to save.
@@ -1260,12 +1280,14 @@ bool knobs_default(const vr_ctx *c)
 {
     const vr_ctx::Knobs &k = c->knobs;
     return k.pipeline < 0 && k.pair < 0 && k.pair_lanes == 0 && k.grad_field < 0 && k.alt < 0 &&
-           k.tile_order == 0;
+           k.tile_order == 0 && k.field_order < 0;
 }
 bool want_ymajor(const vr_ctx *c, const vr_params *p, bool field, bool field_half, bool pipelined)
 {
     if (!pipelined || c->tf_n > (uint32_t)kTfLds) return false;
-    if (p->shading ? !(field && field_half && p->exact_gradient == 0) : field) return false;
+    // its kernels index elements with 32 bits (a 2^32-element volume is 34 GB of bricks)
+    if (c->brick_bytes / element_size(ST_F32) >= 0xFFFF0000ull) return false;
+    if (p->shading ?!(field && field_half && p->exact_gradient == 0) : field) return false;
     if (c->knobs.alt >= 0) return c->knobs.alt == 5;
     return knobs_default(c) && c->dense_rows && c->ray_axis == 1 &&
            c->brick_bytes > kInfinityCacheBytes;
@@ -1368,6 +1390,72 @@ int ensure_alt(vr_ctx *c, int lay, hipStream_t s, bool *ready)
     return record_build(c, s);
 }
 
+// Shaded frames on the y-major copy read the difference field in that copy's order where they
+// can (VR_DERIVED_YMAJOR_FIELD: the same 24-B binary16 elements, bricks in ymajor_slot order and
+// elements y-slowest, so the field loads walk memory as the density loads do; vr_internal.h
+// F32Y).  Wanted wherever the policy sends a shaded frame to the copy; knob VR_KNOB_FIELD_ORDER
+// 0: never, 1: also where VR_KNOB_ALT_GEOMETRY 5 forces the copy.  Opportunistic as the copy:
+// built into room the budget has left, evicting nothing, the first structure evicted
+// (make_room), its absence under the policy no downgrade -- the frame then reads the copy with
+// the z-major field, as before the structure existed.  A frame that gets it builds no z-major
+// field; a view that needs that one evicts this one first.
+#ifndef VR_YFIELD_POLICY  // experiment builds: 0 = the policy never asks for the y-major field
+#define VR_YFIELD_POLICY 1
+#endif
+bool yfield_wanted(const vr_ctx *c, const vr_params *p, bool pipelined)
+{
+    if (c->layout != ST_F32 || !p->shading || p->skip_empty || p->exact_gradient != 0) return false;
+    if (c->knobs.field_order == 0 || !use_grad_field(c, true)) return false;
+    if (!want_ymajor(c, p, true, true, pipelined)) return false;
+    return c->knobs.field_order == 1 || (VR_YFIELD_POLICY && c->knobs.alt < 0);
+}
+// The copy, then the field ((re)built on `s` from the 8^3 bricks when stale); *got: P reads it.
+int ensure_yfield(vr_ctx *c, MarchParams &P, hipStream_t s, bool *got)
+{
+    *got = false;
+    bool ready = false;
+    if (int rc = ensure_alt(c, ST_F32 | kYMajorFlag, s, &ready)) return rc;
+    if (!ready) return VR_OK;
+    const int k = field_scale_log2(c->data_lo, c->data_hi);
+    const size_t bytes = c->brick_bytes / element_size(ST_F32) * kGradElemBytes;
+    if (c->ygrad && c->ygrad_bytes != bytes) {
+        if (int rc = release_async(c, c->ygrad, s)) return rc;
+        c->ygrad = nullptr;
+        c->ygrad_bytes = 0;
+        c->ygrad_valid = false;
+    }
+    if (!c->ygrad) {
+        if (!budget_allows(c, bytes, 0)) return VR_OK;
+        size_t free_b = 0, total_b = 0;
+        void *g = nullptr;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (2ull << 30) ||
+            hipMallocAsync(&g, bytes, s) != hipSuccess) {
+            (void)hipGetLastError();
+            return VR_OK;
+        }
+        c->ygrad = static_cast<float *>(g);
+        c->ygrad_bytes = bytes;
+        c->ygrad_valid = false;
+    }
+    if (!c->ygrad_valid || c->ygrad_scale_log2 != k) {
+        if (c->ygrad_valid)  // rewritten in place: after every frame in flight that may read it
+            if (int rc = fence_others(c, s)) return rc;
+        c->ygrad_valid = false;
+        const hipError_t e = launch_grad_field(static_cast<const float *>(c->bricks), c->ygrad,
+                                               c->nx, c->ny, c->nz, true, k, true, s);
+        if (e != hipSuccess) return hip_fail(c, e, "y-major difference field");
+        c->ygrad_valid = true;
+        c->ygrad_scale_log2 = k;
+        ++c->n_builds;
+        if (int rc = record_build(c, s)) return rc;
+    }
+    P.grad = c->ygrad;
+    P.grad_half = 1;
+    P.grad_ymajor = 1;
+    *got = true;
+    return VR_OK;
+}
+
 // Which kernel runs (vr_variant.h): the facts of a launch, read from P and `layout` after
 // ensure_mip / ensure_derived, use_pair and want_alt have settled what it reads ...
 VariantFacts launch_facts(const vr_ctx *c, const vr_params *p, const MarchParams &P, int layout,
@@ -1399,10 +1487,14 @@ VariantFacts next_frame_facts(const vr_ctx *c, const vr_params *p)
         return f;
     }
     f.skip = p && p->skip_empty;
-    f.field = f.shade && use_grad_field(c, p->exact_gradient == 0) && c->grad && c->grad_valid;
-    f.field_half = f.field && p->exact_gradient == 0;
     const uint32_t tiles = ((c->width + 15) / 16) * ((c->height + kMarchRows - 1) / kMarchRows);
     f.pipeline = use_pipeline(f.shade, tiles, c);
+    // (either field: the y-major one where the next frame would read it, with its copy)
+    const bool yfield = f.shade && yfield_wanted(c, p, f.pipeline != 0) && c->ygrad &&
+                        c->ygrad_valid && c->alt[kYMajorAlt].valid;
+    f.field = f.shade && use_grad_field(c, p->exact_gradient == 0) &&
+              ((c->grad && c->grad_valid) || yfield);
+    f.field_half = f.field && p->exact_gradient == 0;
     if (p)
         if (const int lay = want_alt(c, p, false, f.field != 0, f.field_half != 0, f.pipeline != 0);
             lay != c->layout && c->alt[alt_index(lay)].valid)
@@ -1531,7 +1623,7 @@ int replicate_volume(vr_ctx *c)
             d->vmax = src->vmax;
             d->data_lo = src->data_lo;
             d->data_hi = src->data_hi;
-            d->range_valid = d->dist_valid = d->grad_valid = false;
+            d->range_valid = d->dist_valid = d->grad_valid = d->ygrad_valid = false;
         }
     }
     for (size_t k = 1; k < n; ++k)
@@ -1565,6 +1657,7 @@ int *knob_slot(vr_ctx *c, int knob)
         case VR_KNOB_NARROW: return &c->knobs.narrow;
         case VR_KNOB_ALT_GEOMETRY: return &c->knobs.alt;
         case VR_KNOB_MIP_INFLIGHT: return &c->knobs.mip_inflight;
+        case VR_KNOB_FIELD_ORDER: return &c->knobs.field_order;
         default: return nullptr;
     }
 }
@@ -2350,6 +2443,13 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
         rc = ensure_mip(c, p, P, M, s, &refused);
         if (rc) return rc;
     } else {
+        // a shaded frame bound for the y-major copy: that copy and the field in its order
+        if (yfield_wanted(c, p, P.pipelined != 0) && !use_pair(c, P, p)) {
+            bool got = false;
+            if ((rc = wait_builds(c, s)) != VR_OK || (rc = ensure_yfield(c, P, s, &got)) != VR_OK)
+                return rc;
+            if (!got && c->knobs.field_order == 1) refused = VR_DERIVED_YMAJOR_FIELD;
+        }
         rc = ensure_derived(c, p, P, s, &refused);
         if (rc) return rc;
         if (use_pair(c, P, p)) {  // L lanes per ray on 16 x (16 / L) tiles (march_pair_kernel)
@@ -2374,6 +2474,7 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
                 P.vol_bytes = c->alt[alt_index(lay)].bytes;
                 P.nbx = bricks_for(c->nx, 0, layout);
                 P.nby = bricks_for(c->ny, 1, layout);
+                P.nbz = bricks_for(c->nz, 2, layout);
             } else {
                 // the y-major copy is opportunistic (it evicts nothing, so under a full budget
                 // it is often absent): the frame then runs what it ran before the copy existed,
@@ -2382,6 +2483,8 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
             }
         }
     }
+    if (P.grad_ymajor && !(layout & kYMajorFlag))
+        return fail(c, VR_EIO, "internal: the y-major field without the y-major copy");
     if (!launch) return VR_OK;
     if (refused) {  // a budget-forced downgrade: recorded (vr_memory_report), never silent
         ++c->n_downgrades;
@@ -2609,8 +2712,16 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
     uint32_t refused = 0;  // a count is not a frame: not a downgrade
     MipArgs M{nullptr, 0};
     const bool mip = range_mode(c);
+    // The count of a frame that reads the y-major field builds no z-major field for itself (it
+    // would take the budget the y-major one needs, 3x the bricks each): the counting kernel walks
+    // the 8^3 bricks, and the counts do not depend on the gradient (shading leaves alpha alone),
+    // so without a field in place it runs the stencil variant.
+    const bool no_field = !mip && !(c->grad && c->grad_valid) &&
+                          yfield_wanted(c, p, P.pipelined != 0) && !use_pair(c, P, p);
+    if (no_field) P.grad_ymajor = 1;  // ensure_derived: no field build
     rc = mip ? ensure_mip(c, p, P, M, nullptr, &refused) : ensure_derived(c, p, P, nullptr, &refused);
     if (rc) return rc;
+    P.grad_ymajor = 0;
     HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
     FrameVariant v;
     resolve_variant(launch_facts(c, p, P, c->layout, true), &v);
@@ -2779,6 +2890,13 @@ const char *vr_debug_last_kernel_name(const vr_ctx *c)
     thread_local std::string name;
     name = c->last_mpr_name.empty() ? variant_kernel_name(c->last_variant) : c->last_mpr_name;
     return name.c_str();
+}
+
+uint64_t vr_debug_ymajor_field_bytes(const vr_ctx *c)
+{
+    if (!c) return 0;
+    if (is_group(c)) return vr_debug_ymajor_field_bytes(c->members[0]);
+    return c->ygrad ? c->ygrad_bytes : 0;
 }
 
 uint64_t vr_debug_ymajor_copy_bytes(const vr_ctx *c)

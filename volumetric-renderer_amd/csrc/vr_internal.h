@@ -196,13 +196,16 @@ struct F32H {
     float v;
 };
 // The y-major copy (kYMajorFlag, kernel tags F32Y and, read with the binary16 field, F32HY): the
-// GeomWide brick grid in brick_slot order, but every element a y-pair {v(x,y,z), v(x,y+1,z)} and
-// the elements of a brick ordered x + EX (z + EZ y) -- y slowest.  A sample is 2 x 16-B loads at
+// GeomWide brick grid with the bricks in ymajor_slot order (x, then z, then y: the bricks along a
+// ray that runs along y are nbx * nbz slots apart, those under an image tile adjacent, as the
+// z-pair bricks are for a ray along z), every element a y-pair {v(x,y,z), v(x,y+1,z)} and the
+// elements of a brick ordered x + EX (z + EZ y) -- y slowest.  A sample is 2 x 16-B loads at
 // e and e + EX (elements x, x + 1 of rows z and z + 1).  For dense-row views whose ray runs along
 // y: a step of 2.56 voxels then passes whole 648-B y-layers by, where in the z-pair bricks it
 // reads rows y and y + 1 of every z-layer, i.e. nearly every line.  The
-// difference field stays z-major and shared: a cell's field element is at ymajor_field_delta
-// elements from its y-major one.
+// difference field exists in both orders: the y-major one (kernel flag MarchParams::grad_ymajor)
+// has a cell's 24-B element at the copy's element index; the z-major one, shared with the 8^3
+// bricks, has it at cell_offset<float> in brick_slot order.
 struct F32Y {
     float v;
 };
@@ -224,31 +227,55 @@ __host__ __device__ constexpr int ymajor_field_delta(uint32_t yl, uint32_t zl)
 {
     return GeomWide::EX * (GeomWide::BY * (int)zl - GeomWide::BZ * (int)yl);
 }
-// Element index of padded cell (pi, pj, pk) in the y-major copy; *field_delta (when not null):
-// what to add to reach the same cell's element in the z-major layout.
+// Memory slot of brick (bx, by, bz) in the y-major structures: x fastest, then z, then y (the
+// mirror image of brick_slot's x, y, z; no brick groups).
+__host__ __device__ constexpr uint32_t ymajor_slot(uint32_t bx, uint32_t by, uint32_t bz,
+                                                   uint32_t nbx, uint32_t nbz)
+{
+    return bx + nbx * (bz + nbz * by);
+}
+// Inverse of ymajor_slot.
+__host__ __device__ constexpr void ymajor_coords(uint32_t slot, uint32_t nbx, uint32_t nbz,
+                                                 uint32_t &bx, uint32_t &by, uint32_t &bz)
+{
+    bx = slot % nbx;
+    bz = (slot / nbx) % nbz;
+    by = slot / (nbx * nbz);
+}
+// Element index of padded cell (pi, pj, pk) in the y-major copy (and the y-major field);
+// *field_delta (when not null): the in-brick part of the way to the same cell's element in the
+// z-major layout (the bricks' slots differ as well: ymajor_slot against brick_slot).
 __host__ __device__ constexpr size_t ymajor_cell_offset(uint32_t pi, uint32_t pj, uint32_t pk,
-                                                        uint32_t nbx, uint32_t nby,
+                                                        uint32_t nbx, uint32_t nbz,
                                                         int *field_delta = nullptr)
 {
     using G = GeomWide;
     const uint32_t bx = pi / G::BX, by = pj / G::BY, bz = pk / G::BZ;
     const uint32_t xl = pi - bx * G::BX, yl = pj - by * G::BY, zl = pk - bz * G::BZ;
     if (field_delta) *field_delta = ymajor_field_delta(yl, zl);
-    return (size_t)brick_slot(bx, by, bz, nbx, nby) * (size_t)G::Elems + ymajor_local(xl, yl, zl);
+    return (size_t)ymajor_slot(bx, by, bz, nbx, nbz) * (size_t)G::Elems + ymajor_local(xl, yl, zl);
 }
 namespace ymajor_check {
-// Over a 3 x 2 x 2-brick grid: every element (cells and apron) of every brick maps into its own
+// Over an NBX x NBY x NBZ-brick grid: ymajor_slot is a bijection onto [0, bricks) with
+// ymajor_coords its inverse; every element (cells and apron) of every brick maps into its own
 // brick's [0, 729) exactly once, and the z-major index is the y-major one + the field delta.
+template <uint32_t NBX, uint32_t NBY, uint32_t NBZ>
 constexpr bool map_ok()
 {
     using G = GeomWide;
-    constexpr uint32_t nbx = (3 + kGroupMask) & ~kGroupMask, nby = (2 + kGroupMask) & ~kGroupMask,
-                       nbz = nby;
+    constexpr uint32_t nbx = NBX, nby = NBY, nbz = NBZ;
+    bool slot_seen[nbx * nby * nbz] = {};
     for (uint32_t bz = 0; bz < nbz; ++bz)
         for (uint32_t by = 0; by < nby; ++by)
             for (uint32_t bx = 0; bx < nbx; ++bx) {
+                const uint32_t slot = ymajor_slot(bx, by, bz, nbx, nbz);
+                if (slot >= nbx * nby * nbz || slot_seen[slot]) return false;
+                slot_seen[slot] = true;
+                uint32_t cx = 0, cy = 0, cz = 0;
+                ymajor_coords(slot, nbx, nbz, cx, cy, cz);
+                if (cx != bx || cy != by || cz != bz) return false;
                 bool seen[G::EX * G::EY * G::EZ] = {};
-                const size_t base = (size_t)brick_slot(bx, by, bz, nbx, nby) * (size_t)G::Elems;
+                const size_t base = (size_t)slot * (size_t)G::Elems;
                 for (uint32_t zl = 0; zl < (uint32_t)G::EZ; ++zl)
                     for (uint32_t yl = 0; yl < (uint32_t)G::EY; ++yl)
                         for (uint32_t xl = 0; xl < (uint32_t)G::EX; ++xl) {
@@ -261,14 +288,15 @@ constexpr bool map_ok()
                             if (xl < (uint32_t)G::BX && yl < (uint32_t)G::BY && zl < (uint32_t)G::BZ) {
                                 int fd = 0;
                                 const size_t e = ymajor_cell_offset(bx * G::BX + xl, by * G::BY + yl,
-                                                                    bz * G::BZ + zl, nbx, nby, &fd);
+                                                                    bz * G::BZ + zl, nbx, nbz, &fd);
                                 if (e != base + l || fd != ymajor_field_delta(yl, zl)) return false;
                             }
                         }
             }
     return true;
 }
-static_assert(map_ok(), "the y-major map is a bijection onto each brick, 72 (zl - yl) from z-major");
+static_assert(map_ok<3, 2, 2>(), "the y-major maps are bijections, 72 (zl - yl) from z-major");
+static_assert(map_ok<2, 1, 3>() && map_ok<1, 3, 2>(), "... also where nby != nbz");
 static_assert(GeomWide::BX != 8 || GeomWide::BY != 8 || GeomWide::BZ != 8 ||
                   ymajor_field_delta(3, 5) == 72 * (5 - 3),
               "8^3 cells: l_zmajor - l_ymajor == 72 (zl - yl)");
@@ -434,6 +462,10 @@ struct MarchParams {
     // bytes of the volume copy P.vol points at and of the output buffer (bounds-checking
     // debug builds, -DVR_BOUNDS_CHECK: an out-of-range access is printed and skipped)
     unsigned long long vol_bytes, out_bytes;
+    // the y-major structures (F32Y): bricks per axis z (ymajor_slot), and whether `grad` is the
+    // y-major binary16 field (a cell's element at the copy's element index) or the z-major one
+    uint32_t nbz;
+    int32_t grad_ymajor;
 };
 
 // Launchers (vr_kernels.hip).  All asynchronous on `stream`.
@@ -587,9 +619,11 @@ constexpr int kSkipCap = 16;
 // f32 gradient field (see MarchParams::grad) from the bricked density: same brick grid.
 constexpr size_t kGradElemBytes = 24;
 // half: the binary16 field of MarchParams::grad_half, each difference times 2^scale_log2 and
-// clamped to +-65504 (NaN kept) before rounding to nearest even
+// clamped to +-65504 (NaN kept) before rounding to nearest even.  ymajor (half only): the same
+// elements in the y-major copy's brick and element order (MarchParams::grad_ymajor)
 hipError_t launch_grad_field(const float *bricks, float *grad, uint32_t nx, uint32_t ny,
-                             uint32_t nz, bool half, int scale_log2, hipStream_t stream);
+                             uint32_t nz, bool half, int scale_log2, bool ymajor,
+                             hipStream_t stream);
 // The f32 copy in layout `storage` (kAltFlag / kPlainF32Flag / kStencilF32Flag) straight from the
 // 8^3 z-pair bricks: the same bytes as launch_unbrick + launch_brick_from_linear.  kYMajorFlag:
 // the y-major copy (F32Y above), one pass of its own over the same bricks.

@@ -159,6 +159,7 @@ constexpr int kQuadWords = sizeof(VT) == 1 ? 1 : 2;
 // Element index of padded cell (pi, pj, pk) in the bricked layout (vr_internal.h).  64-bit:
 // a 2048^3 volume has 257^3 x 729 elements.  (A 32-bit index with SGPR-base loads for
 // volumes < 4 GiB measured slower on the shaded kernel and on the diagonal view.)
+// (kYMajor: the last argument is nbz, the y-major structures' slot order, not nby)
 template <typename VT>
 __device__ __forceinline__ size_t cell_offset(int pi, int pj, int pk, uint32_t nbx, uint32_t nby)
 {
@@ -1255,7 +1256,8 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
         // The TF is LDS-resident (host guarantees tf_n <= kTfLds for PIPE).
         struct Stage {
             CellRaw<VT> w;  // loaded words, decoded at consume
-            size_t ce;      // the cell's element (kYMajor: in the z-major layout, the field's)
+            // the cell's element (kYMajor: the field's, in either order; 32-bit)
+            std::conditional_t<kYMajor<VT>, uint32_t, size_t> ce;
             float ax, ay, az;
             int pi, pj, pk;
             bool ok, slab;
@@ -1278,14 +1280,17 @@ __device__ __forceinline__ void march_strip(const MarchParams &P, LdsF4 *s_tf,
             S.pj = j + kPad;
             S.pk = kk + kPad;
             if constexpr (kYMajor<VT>) {
-                // the stage keeps the z-major element, where the shared difference field has
-                // this cell; the y-major one, that many elements before it, only issues the
-                // loads (no register beyond the z-pair kernels')
-                S.ce = cell_offset<float>(S.pi, S.pj, S.pk, P.nbx, P.nby);
-                size_t e = (size_t)((long)S.ce -
-                                    ymajor_field_delta((uint32_t)S.pj % (uint32_t)G::BY,
-                                                       (uint32_t)S.pk % (uint32_t)G::BZ));
-                if (VR_OOB(3, e * kElemBytes<VT>, P.vol_bytes)) e = S.ce = 0;
+                // the stage keeps the field's element of this cell: with the y-major field
+                // (P.grad_ymajor, wave-uniform) the copy's own; with the shared z-major field
+                // that one, and the copy's element -- another brick slot (ymajor_slot against
+                // brick_slot), another in-brick order -- only issues the loads.  32-bit indices
+                // (the host sends no volume of 2^32 elements here): the second index costs
+                // one register, which a 64-bit one would not leave this kernel
+                uint32_t e = (uint32_t)cell_offset<VT>(S.pi, S.pj, S.pk, P.nbx, P.nbz);
+                S.ce = (!SHADE || P.grad_ymajor)
+                           ? e
+                           : (uint32_t)cell_offset<float>(S.pi, S.pj, S.pk, P.nbx, P.nby);
+                if (VR_OOB(3, (size_t)e * kElemBytes<VT>, P.vol_bytes)) e = S.ce = 0;
                 Cell8<VT>::issue(S.w, vol, e);
             } else {
                 S.ce = cell_offset<VT>(S.pi, S.pj, S.pk, P.nbx, P.nby);
@@ -2572,9 +2577,10 @@ __global__ __launch_bounds__(256) void rebrick_ymajor_kernel(const float *__rest
                                                              uint32_t nby, size_t nbricks)
 {
     using G = GeomWide;
-    for (size_t bidx = blockIdx.x; bidx < nbricks; bidx += gridDim.x) {
+    const uint32_t nbz = (uint32_t)(nbricks / ((size_t)nbx * nby));
+    for (size_t bidx = blockIdx.x; bidx < nbricks; bidx += gridDim.x) {  // bidx: the ymajor_slot
         uint32_t bx, by, bz;
-        brick_coords((uint32_t)bidx, nbx, nby, bx, by, bz);
+        ymajor_coords((uint32_t)bidx, nbx, nbz, bx, by, bz);
         for (uint32_t l = threadIdx.x; l < (uint32_t)G::Elems; l += blockDim.x) {
             const uint32_t lx = l % G::EX, lzy = l / G::EX, lz = lzy % G::EZ, ly = lzy / G::EZ;
             float2 v = make_float2(0.0f, 0.0f);  // (and the brick's alignment padding)
@@ -2608,11 +2614,16 @@ __device__ __forceinline__ _Float16 field_half(float d, float scale)
 // element's differences read from there (the same subtractions, so the same bits): one global
 // load per staged voxel instead of 12 (f32) or 24 (binary16) per element.  Each brick's
 // elements are written contiguously.
+// ymajor (binary16 only): the y-major field -- the same 24-B elements in the y-major copy's
+// order (vr_internal.h: bricks in ymajor_slot order, a brick's elements at ymajor_local), read
+// from the same z-pair bricks; only the place of an element in the staged brick and the brick's
+// place in memory differ.
 template <bool H>
 __global__ __launch_bounds__(256) void grad_field_kernel(const float *__restrict__ bricks,
                                                          float *__restrict__ grad, uint32_t nx,
                                                          uint32_t ny, uint32_t nz, uint32_t nbx,
-                                                         uint32_t nby, size_t nbricks, float scale)
+                                                         uint32_t nby, size_t nbricks, float scale,
+                                                         uint32_t ymajor)
 {
     using G = GeomWide;
     constexpr int LX = G::EX + 2, LY = G::EY + 2 + (H ? 1 : 0), LZ = G::EZ + 3;
@@ -2623,7 +2634,10 @@ __global__ __launch_bounds__(256) void grad_field_kernel(const float *__restrict
     const uint32_t nbz = (uint32_t)(nbricks / ((size_t)nbx * nby));
     for (size_t bidx = blockIdx.x; bidx < nbricks; bidx += gridDim.x) {
         uint32_t bx, by, bz;
-        brick_coords((uint32_t)bidx, nbx, nby, bx, by, bz);
+        if (H && ymajor)
+            ymajor_coords((uint32_t)bidx, nbx, nbz, bx, by, bz);
+        else
+            brick_coords((uint32_t)bidx, nbx, nby, bx, by, bz);
         const int x0 = (int)(bx * G::BX) - 1, y0 = (int)(by * G::BY) - 1, z0 = (int)(bz * G::BZ) - 1;
         __syncthreads();  // the previous brick's elements have read the box and left ostage
         // two z-slices per load: the z-pair element at (x, y, z) holds {v(z), v(z + 1)}, the
@@ -2650,6 +2664,7 @@ __global__ __launch_bounds__(256) void grad_field_kernel(const float *__restrict
                 o[0] = o[1] = o[2] = make_uint2(0u, 0u);
                 continue;
             }
+            if (H && ymajor) o = ostage + 3 * ymajor_local(lx, lyy, lz);
             // box index of padded voxel (x0 + 1 + lx + dx, y0 + 1 + lyy + dy, z0 + 1 + lz + dz)
             const int c = ((int)lz + 1) * (LX * LY) + ((int)lyy + 1) * LX + ((int)lx + 1);
             if constexpr (H) {
@@ -3141,18 +3156,19 @@ hipError_t launch_brick_range(int storage, const void *bricks, uint32_t nbx, uin
 }
 
 hipError_t launch_grad_field(const float *bricks, float *grad, uint32_t nx, uint32_t ny,
-                             uint32_t nz, bool half, int scale_log2, hipStream_t s)
+                             uint32_t nz, bool half, int scale_log2, bool ymajor, hipStream_t s)
 {
+    if (ymajor && !half) return hipErrorInvalidValue;  // the y-major field is binary16 only
     const uint32_t nbx = bricks_for(nx, 0, ST_F32), nby = bricks_for(ny, 1, ST_F32),
                    nbz = bricks_for(nz, 2, ST_F32);
     const size_t total = (size_t)nbx * nby * nbz;  // bricks
     const float scale = std::ldexp(1.0f, scale_log2);
     if (half)
         hipLaunchKernelGGL(grad_field_kernel<true>, dim3(grid_bricks(total)), dim3(256), 0, s,
-                           bricks, grad, nx, ny, nz, nbx, nby, total, scale);
+                           bricks, grad, nx, ny, nz, nbx, nby, total, scale, ymajor ? 1u : 0u);
     else
         hipLaunchKernelGGL(grad_field_kernel<false>, dim3(grid_bricks(total)), dim3(256), 0, s,
-                           bricks, grad, nx, ny, nz, nbx, nby, total, scale);
+                           bricks, grad, nx, ny, nz, nbx, nby, total, scale, 0u);
     return hipGetLastError();
 }
 

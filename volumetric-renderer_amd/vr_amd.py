@@ -77,7 +77,7 @@ class vr_dist_host_profile(C.Structure):  # vr_dist.h
 
 # vr.h enum vr_derived (vr_memory_info.last_downgrade)
 DERIVED = {1: "field", 2: "oblique_copy", 3: "plain_copy", 4: "stencil_copy", 5: "skip",
-           6: "ymajor_copy"}
+           6: "ymajor_copy", 7: "ymajor_field"}
 
 
 class vr_member_timing(C.Structure):  # vr_debug.h (ABI 7)
@@ -135,7 +135,7 @@ DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_memb
                  "vr_debug_create_members", "vr_debug_fail_member",
                  "vr_debug_host_profile_enable", "vr_debug_host_profile_member",
                  "vr_debug_variant_name", "vr_debug_last_kernel_name",
-                 "vr_debug_ymajor_copy_bytes"]
+                 "vr_debug_ymajor_copy_bytes", "vr_debug_ymajor_field_bytes"]
 # include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
 MODE_COMPOSITE, MODE_MIP = 0, 1
@@ -152,10 +152,10 @@ AXIS_SAGITTAL, AXIS_CORONAL, AXIS_AXIAL = 0, 1, 2
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
 KNOBS = {"pipeline": 1, "pair": 2, "pair_lanes": 3, "grad_field": 4, "u8_layout": 6,
-         "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10}
+         "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10, "field_order": 11}
 KNOB_AUTO = {"pipeline": -1, "pair": -1, "pair_lanes": 0, "grad_field": -1,
              "u8_layout": -1, "tile_order": 0, "narrow": 1, "alt_geometry": -1,
-             "mip_inflight": 0}
+             "mip_inflight": 0, "field_order": -1}
 
 ABI_VERSION = 9  # include/vr/vr.h VR_ABI_VERSION
 _LIB = None
@@ -248,6 +248,7 @@ def lib() -> C.CDLL:
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
         "vr_debug_last_kernel_name": (C.c_char_p, [vp]),
         "vr_debug_ymajor_copy_bytes": (C.c_uint64, [vp]),
+        "vr_debug_ymajor_field_bytes": (C.c_uint64, [vp]),
         "vr_cam_init": (None, [C.POINTER(vr_orbit_camera)]),
         "vr_cam_rotate": (None, [C.POINTER(vr_orbit_camera), f32, f32]),
         "vr_cam_zoom": (None, [C.POINTER(vr_orbit_camera), f32]),
@@ -713,6 +714,7 @@ class OffscreenPass:
         r = {n: int(getattr(m, n)) for n, _ in vr_memory_info._fields_}
         # the y-major copy has no field of its own in the ABI 9 struct (vr_debug.h)
         r["ymajor_copy_bytes"] = int(lib().vr_debug_ymajor_copy_bytes(self._ctx))
+        r["ymajor_field_bytes"] = int(lib().vr_debug_ymajor_field_bytes(self._ctx))
         return r
 
     def prepare(self, camera, params):
