@@ -59,6 +59,7 @@
 #include "vr_modes.h"
 #include "vr_iso.h"
 #include "vr_mpr.h"
+#include "vr_hist.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -296,6 +297,31 @@ class BasicOffscreenPass {
     {
         check(vr_mpr_render_device(ctx_, &plane, &params_, out_dev, fmt, hip_stream));
     }
+
+    // Extension (vr_hist.h): the value histogram of the resident volume over [lo, hi] in nbins
+    // bins -- of the whole volume, or of the half-open voxel box [box_min, box_max) -- computed on
+    // the device; the counts are returned, the out-of-range counts and the exact data range go to
+    // *info (when not null).  The context's state and every frame stay as they are.
+    std::vector<uint64_t> histogram(uint32_t nbins, float lo, float hi, vr_hist_info *info = nullptr,
+                                    const uint32_t *box_min = nullptr, const uint32_t *box_max = nullptr)
+    {
+        vr_hist_request req{};
+        req.lo = lo;
+        req.hi = hi;
+        req.nbins = nbins;
+        req.use_box = box_min && box_max ? 1u : 0u;
+        for (int a = 0; a < 3 && req.use_box; ++a) {
+            req.box_min[a] = box_min[a];
+            req.box_max[a] = box_max[a];
+        }
+        std::vector<uint64_t> bins(nbins && nbins <= VR_HIST_MAX_BINS ? nbins : 1u);
+        vr_hist_info local{};
+        check(vr_histogram(ctx_, &req, bins.data(), info ? info : &local));
+        return bins;
+    }
+    // Extension (vr_hist.h): a new value window (Dataset.min / max) for the resident voxels,
+    // without the re-upload volume_dataset_changed would need.
+    void value_range_changed(float vmin, float vmax) { check(vr_set_value_range(ctx_, vmin, vmax)); }
 
     const std::vector<uint32_t> &image() const { return image_; }
     vr_params &params() { return params_; }  // step, ERT, shading (reference defaults)

@@ -46,10 +46,13 @@ enum vr_knob {
                                launch allows it (2, the retired z-pair sparse copy: EINVAL) */
     VR_KNOB_MIP_INFLIGHT = 10, /* VR_MODE_MIP and VR_MODE_ISO (vr_modes.h): samples of a ray whose
                                loads are in flight together: 0 auto, 1, 2 or 4 (same bytes) */
-    VR_KNOB_FIELD_ORDER = 11  /* shaded frames that read the y-major copy: -1 auto (the y-major
+    VR_KNOB_FIELD_ORDER = 11, /* shaded frames that read the y-major copy: -1 auto (the y-major
                                binary16 field where the policy chose the copy), 0 the z-major
                                difference field only, 1 the y-major field on every frame that
                                reads the copy, at any volume size (same bytes)              */
+    VR_KNOB_HIST_AGG = 12     /* vr_histogram (vr_hist.h): -1 auto, 0 every lane adds to its
+                               bin's LDS counter, 1 lanes that share the wave's leading bin add
+                               once by their count (same counts)                            */
 };
 
 /* Per-device timing of a context (ABI 7), so that a multi-GPU frame that runs slow names its

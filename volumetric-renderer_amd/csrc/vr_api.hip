@@ -11,6 +11,7 @@
 #include "../../include/vr/vr_modes.h"
 #include "../../include/vr/vr_iso.h"
 #include "../../include/vr/vr_mpr.h"
+#include "../../include/vr/vr_hist.h"
 #include "vr_internal.h"
 #include "vr_group.h"
 
@@ -133,7 +134,7 @@ struct vr_ctx {
     uint64_t build_gen = 0;  // records of built_ev so far
     uint64_t frame_no = 0;  // launches so far (the derived structures' recency)
     FrameVariant last_variant;  // the last frame or count launch (vr_debug_last_kernel_name)
-    std::string last_mpr_name;  // not empty: an MPR launch (vr_mpr.h) came after it
+    std::string last_mpr_name;  // not empty: an MPR or histogram launch (vr_mpr.h, vr_hist.h) came after it
     // derived-structure history (vr_memory_report, ABI 9)
     uint64_t n_builds = 0, n_evictions = 0, n_downgrades = 0;
     uint32_t last_downgrade = 0;
@@ -144,6 +145,8 @@ struct vr_ctx {
     // vr_mpr_render (host output): its image, whose size is the plane's and not the framebuffer's
     void *mpr_dev = nullptr;
     size_t mpr_bytes = 0;
+    // vr_histogram (vr_hist.h): HistArgs::out (kHistOutWords 64-bit words), then the edge table
+    void *hist_dev = nullptr;
     // vr_render (host output): row bands rendered on two streams while finished bands copy
     // to the host on a third, so the PCIe copy hides behind the rest of the frame
     hipStream_t band_stream[2] = {nullptr, nullptr};
@@ -159,7 +162,7 @@ struct vr_ctx {
     // product path never reads the process environment
     struct Knobs {
         int pipeline = -1, pair = -1, pair_lanes = 0, grad_field = -1, u8_layout = -1,
-            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0, field_order = -1;
+            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0, field_order = -1, hist_agg = -1;
     } knobs;
     // multi-device context (vr_create_mask): one member context per device of the mask, the
     // volume/TF/slicing replicated on each, frames rendered across them by `group`
@@ -1658,6 +1661,7 @@ int *knob_slot(vr_ctx *c, int knob)
         case VR_KNOB_ALT_GEOMETRY: return &c->knobs.alt;
         case VR_KNOB_MIP_INFLIGHT: return &c->knobs.mip_inflight;
         case VR_KNOB_FIELD_ORDER: return &c->knobs.field_order;
+        case VR_KNOB_HIST_AGG: return &c->knobs.hist_agg;
         default: return nullptr;
     }
 }
@@ -1961,6 +1965,7 @@ void vr_destroy(vr_ctx *c)
     if (c->counters) hipFree(c->counters);
     if (c->frame_dev) hipFree(c->frame_dev);
     if (c->mpr_dev) hipFree(c->mpr_dev);
+    if (c->hist_dev) hipFree(c->hist_dev);
     for (auto e : c->band_ev)
         if (e) hipEventDestroy(e);
     for (auto st : c->band_stream)
@@ -3123,6 +3128,139 @@ int vr_mpr_axis_plane(int axis, float position, uint32_t width, uint32_t height,
     pl.nsamples = nsamples;
     pl.op = op;
     *out = pl;
+    return VR_OK;
+}
+
+// ---- value histogram and value window (include/vr/vr_hist.h) ---------------------------------
+
+int vr_hist_edges(float lo, float hi, uint32_t nbins, float *edges_out)
+{
+    if (!edges_out) return fail(nullptr, VR_EINVAL, "edges is NULL");
+    if (!hist_range_ok(lo, hi, nbins))
+        return fail(nullptr, VR_EINVAL, "histogram needs finite lo < hi and 1 <= nbins <= 4096");
+    hist_edges(lo, hi, nbins, edges_out);
+    return VR_OK;
+}
+
+int vr_hist_window(const uint64_t *bins, uint32_t nbins, float lo, float hi, double p_lo,
+                   double p_hi, float *vmin_out, float *vmax_out)
+{
+    if (!hist_window(bins, nbins, lo, hi, p_lo, p_hi, vmin_out, vmax_out))
+        return fail(nullptr, VR_EINVAL,
+                    "histogram window needs bins with a count, finite lo < hi, 1 <= nbins <= 4096 "
+                    "and 0 <= p_lo < p_hi <= 1");
+    return VR_OK;
+}
+
+int vr_histogram(vr_ctx *c, const vr_hist_request *req, uint64_t *bins_host, vr_hist_info *info)
+{
+    if (!c || !req || !bins_host || !info) return fail(c, VR_EINVAL, "NULL argument");
+    if (!hist_range_ok(req->lo, req->hi, req->nbins))
+        return fail(c, VR_EINVAL, "histogram needs finite lo < hi and 1 <= nbins <= 4096");
+    if (req->use_box > 1) return fail(c, VR_EINVAL, "histogram use_box must be 0 or 1");
+    if (is_group(c)) {  // on the lowest device, which holds a replica
+        if (int rc = group_idle(c)) return rc;
+        return member_rc(c, c->members[0], vr_histogram(c->members[0], req, bins_host, info));
+    }
+    if (!c->bricks) return fail(c, VR_EINVAL, "no volume");
+    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
+    HistArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.nwork = 1;
+    for (int a = 0; a < 3; ++a) {
+        A.box_min[a] = req->use_box ? req->box_min[a] : 0u;
+        A.box_max[a] = req->use_box ? req->box_max[a] : dims[a];
+        if (A.box_min[a] >= A.box_max[a] || A.box_max[a] > dims[a])
+            return fail(c, VR_EINVAL, "histogram box is empty or beyond the volume");
+        // the bricks of padded indices box_min + kPad .. box_max - 1 + kPad
+        const uint32_t cells = (uint32_t)brick_cells(c->layout, a);
+        A.b0[a] = (A.box_min[a] + kPad) / cells;
+        A.nb[a] = (A.box_max[a] - 1 + kPad) / cells - A.b0[a] + 1;
+        A.nwork *= A.nb[a];
+    }
+    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
+    const size_t out_bytes = kHistOutWords * sizeof(unsigned long long);
+    if (!c->hist_dev)
+        HIP_TRY(c, hipMalloc(&c->hist_dev, out_bytes + kHistMaxBins * sizeof(float)),
+                "hipMalloc(histogram)");
+    float edges[kHistMaxBins];
+    hist_edges(req->lo, req->hi, req->nbins, edges);
+    A.vol = c->bricks;
+    A.out = static_cast<unsigned long long *>(c->hist_dev);
+    A.edges = reinterpret_cast<const float *>(static_cast<char *>(c->hist_dev) + out_bytes);
+    A.scale = hist_scale(req->lo, req->hi, req->nbins);
+    A.lo = req->lo;
+    A.hi = req->hi;
+    A.nbins = req->nbins;
+    A.nbx = bricks_for(c->nx, 0, c->layout);
+    A.nby = bricks_for(c->ny, 1, c->layout);
+    HIP_TRY(c, hipMemcpy(const_cast<float *>(A.edges), edges, req->nbins * sizeof(float),
+                         hipMemcpyHostToDevice), "hipMemcpy(histogram edges)");
+    HIP_TRY(c, hipMemsetAsync(A.out, 0, out_bytes, nullptr), "hipMemset(histogram)");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    const bool timing = c->timing;
+    if (timing) {
+        e0 = pooled_event(c);
+        e1 = pooled_event(c);
+        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
+        HIP_TRY(c, hipEventRecord(e0, nullptr), "hipEventRecord");
+    }
+    std::string name;
+    // The kernel form (knob VR_KNOB_HIST_AGG overrides).  Plain 8-bit bricks count raw codes, and
+    // there a constant volume -- every lane on one LDS word -- takes 4.0x the Gaussians' time unless
+    // the wave's leading code is added once (C4: 3.53 -> 1.07 ms, the Gaussians 0.87 -> 1.14 ms);
+    // the other layouts bin every voxel first, the constant volume costs them 16 % and the
+    // aggregation 10 % on the Gaussians (C3: 0.51 / 0.59 ms against 0.56 / 0.55 ms), so they add
+    // singly (profiles/r15/hist/).
+    const bool agg = c->knobs.hist_agg >= 0 ? c->knobs.hist_agg == 1 : byte_storage(c->layout);
+    HIP_TRY(c, launch_hist(c->layout, agg, A, nullptr, &name), "histogram kernel launch");
+    c->last_mpr_name = name;
+    if (timing) {
+        HIP_TRY(c, hipEventRecord(e1, nullptr), "hipEventRecord");
+        c->ev_pending.emplace_back(e0, e1);
+    }
+    std::vector<unsigned long long> h((size_t)req->nbins + 4);
+    HIP_TRY(c, hipMemcpy(h.data(), A.out, ((size_t)req->nbins + 4) * sizeof(unsigned long long),
+                         hipMemcpyDeviceToHost), "hipMemcpy(histogram)");
+    vr_hist_info I;
+    std::memset(&I, 0, sizeof I);
+    I.below = h[req->nbins + 0];
+    I.above = h[req->nbins + 1];
+    I.nan = h[req->nbins + 2];
+    I.voxels = I.below + I.above + I.nan;
+    for (uint32_t b = 0; b < req->nbins; ++b) {
+        bins_host[b] = h[b];
+        I.voxels += h[b];
+    }
+    auto unorder = [](uint32_t o) {
+        const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    };
+    uint32_t ext[2];
+    std::memcpy(ext, &h[req->nbins + 3], sizeof ext);
+    const bool any = I.voxels > I.nan;
+    I.vmin = any ? unorder(~ext[0]) : INFINITY;
+    I.vmax = any ? unorder(ext[1]) : -INFINITY;
+    *info = I;
+    return VR_OK;
+}
+
+int vr_set_value_range(vr_ctx *c, float vmin, float vmax)
+{
+    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
+    if (is_group(c)) {
+        if (int rc = group_idle(c)) return rc;
+        for (vr_ctx *m : c->members)
+            if (int rc = vr_set_value_range(m, vmin, vmax)) return member_rc(c, m, rc);
+        return VR_OK;
+    }
+    // a frame in flight may read the distance field the next skip_empty frame rebuilds
+    if (int rc = wait_idle(c)) return rc;
+    c->vmin = vmin;
+    c->vmax = vmax;
+    c->dist_valid = false;  // built from vmin and range; the brick ranges and the fields stay
     return VR_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <type_traits>
 
+#include "vr_hist_host.h"
 #include "vr_variant.h"
 
 namespace vr {
@@ -548,6 +549,31 @@ constexpr uint32_t kMprTileOrder(uint32_t nsamples) { return nsamples == 1 ? 1u 
 // the demangled kernel name.  hipErrorInvalidValue: no such layout or operator.
 hipError_t launch_mpr(int layout, bool count, const MprArgs &a, hipStream_t stream,
                       std::string *name);
+// ---- Value histogram (include/vr/vr_hist.h, hist_kernel) ----
+// out: nbins 64-bit counts, then below, above, nan, then one 64-bit slot holding two 32-bit words:
+// ~ordered(minimum) and ordered(maximum) over the non-NaN voxels (minmax_kernel's encoding; the
+// minimum inverted so that both reduce with atomicMax).  The caller zeroes all of it: zero is the
+// identity of every one of these reductions.
+struct HistArgs {
+    const void *vol;        // the base bricks (layout code `layout` of launch_hist)
+    const float *edges;     // nbins lower edges (vr_hist_host.h hist_edges), device
+    unsigned long long *out;
+    double scale;           // hist_scale: the first guess of a bin is (v - lo) * scale
+    float lo, hi;
+    uint32_t nbins;
+    uint32_t nbx, nby;      // bricks per axis (x, y) of the volume
+    uint32_t box_min[3], box_max[3];  // logical voxel indices, half open
+    uint32_t b0[3], nb[3];  // the bricks that hold the box's voxels: first and count per axis
+    uint32_t nwork;         // nb[0] * nb[1] * nb[2]
+};
+constexpr size_t kHistOutWords = (size_t)kHistMaxBins + 4;  // 64-bit words of HistArgs::out
+// workgroups of a histogram launch at most (8 per CU; hist_kernel's 32-bit private counters)
+constexpr uint32_t kHistMaxGrid = 2048;
+// The histogram kernel of a base layout (a storage type, or an 8-bit one | kQuadFlag) over the
+// bricks a.b0 .. a.b0 + a.nb.  agg: the wave-aggregated form (hist_kernel AGG).  *name (when not
+// null): the demangled kernel name.  hipErrorInvalidValue: no such layout, or no work.
+hipError_t launch_hist(int layout, bool agg, const HistArgs &a, hipStream_t stream,
+                       std::string *name);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

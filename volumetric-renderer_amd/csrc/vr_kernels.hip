@@ -2764,6 +2764,197 @@ __global__ __launch_bounds__(256) void range_max_kernel(float2 *__restrict__ ran
                                      fmaxf(fmaxf(s_hi[0], s_hi[1]), fmaxf(s_hi[2], s_hi[3])));
 }
 
+// ---- value histogram (include/vr/vr_hist.h) ---------------------------------------------------
+
+// One pass over the base bricks the box touches, a brick per workgroup iteration (grid-stride over
+// the box's bricks; the others are never read).  Every voxel counts once, through its own element:
+// the cells of the brick (no apron, so no neighbour's copy), component 0 of the element (what
+// unbrick_kernel reads: never the z+1 / yz-quad neighbours), and only where the logical index lies
+// in the box (never the two padding layers nor cells beyond nx, ny, nz).
+// The bin of v is the largest b with e[b] <= v (vr_hist_host.h hist_bin, restated): a first guess
+// in double (the f32 product misplaces a tenth of the edge values, and hi - lo may overflow f32),
+// corrected against the edge table in LDS.  Counters are private to the workgroup, 32-bit in LDS
+// (a workgroup counts nwork / gridDim bricks of at most 512 voxels: with launch_hist's grid that
+// stays below 2^32 for every volume the device can hold), flushed with one 64-bit atomic per
+// non-zero bin.  below / above / nan and the extremes (the integer ordered() form: nothing depends
+// on the float min/max NaN and denormal modes) reduce per wave, then per workgroup, before their
+// atomics, as minmax_kernel's do.  The minimum is kept inverted (~ordered, reduced with max), so
+// an all-zero output block is the identity of every reduction.
+// AGG: lanes whose bin equals the wave's first active lane's add once, by its popcount (the hot
+// bin of a CT-like volume, where all 64 lanes would meet in one LDS word); the others add singly.
+// Plain 8-bit bricks with 8-B rows (the 7 x 8 x 8 geometry of C4 / C5) take the code path: a bin
+// is a function of the code, so the workgroup histograms the 256 raw codes -- a wave per brick, a
+// lane per brick row, one 8-B load for the row's 7 cells, no binning per voxel -- and folds the
+// codes into bins, below / above and the extremes once, at its end, by the same rule.
+template <typename VT>
+constexpr bool kHistCodes = kPlainByte<VT> && GeomOf<VT>::EX == 8 && GeomOf<VT>::BY * GeomOf<VT>::BZ == 64;
+
+template <typename VT, bool AGG>
+__global__ __launch_bounds__(256) void hist_kernel(const HistArgs A)
+{
+    using G = GeomOf<VT>;
+    using V = Vox<VT>;
+    constexpr uint32_t vpe = std::is_same<VT, float>::value ? (uint32_t)kF32VoxelsPerElement
+                                                            : (kPlainByte<VT> ? 1u : 4u);
+    constexpr uint32_t kCells = (uint32_t)(G::BX * G::BY * G::BZ);
+    __shared__ uint32_t s_bins[kHistMaxBins];  // (the code path: its first 256 words, per code)
+    __shared__ float s_edges[kHistMaxBins];
+    __shared__ uint32_t s_red[4][5];
+    const uint32_t tid = threadIdx.x, nbins = A.nbins;
+    for (uint32_t i = tid; i < (kHistCodes<VT> && nbins < 256u ? 256u : nbins); i += 256) {
+        s_bins[i] = 0;
+        if (i < nbins) s_edges[i] = A.edges[i];
+    }
+    __syncthreads();
+    const V *__restrict__ vol = static_cast<const V *>(A.vol);
+    unsigned long long *__restrict__ out = A.out;
+    const float lo = A.lo, hi = A.hi;
+    const double dlo = (double)lo, scale = A.scale;
+    uint32_t below = 0, above = 0, nan = 0, inv_mn = 0, mx = 0;
+    // the bin of v, lo <= v <= hi: the guess, then the edges.  Both neighbours are read at once, so
+    // the common case (the guess, or one off) costs one LDS round trip
+    auto bin_of = [&](float v) __attribute__((always_inline)) {
+        const double g = ((double)v - dlo) * scale;
+        uint32_t b = g >= (double)(nbins - 1) ? nbins - 1 : (g > 0.0 ? (uint32_t)g : 0u);
+        const bool last = b + 1 >= nbins;
+        const float e0 = s_edges[b], e1 = s_edges[last ? b : b + 1];
+        if (!last && e1 <= v) {
+            ++b;
+            while (b + 1 < nbins && s_edges[b + 1] <= v) ++b;
+        } else if (e0 > v) {  // (b > 0: e[0] == lo <= v)
+            --b;
+            while (b > 0 && s_edges[b] > v) --b;
+        }
+        return b;
+    };
+    // one count for word b of s_bins from every lane with `counts`
+    auto add = [&](bool counts, uint32_t b) __attribute__((always_inline)) {
+        if constexpr (AGG) {
+            const unsigned long long active = __ballot(counts);
+            if (active) {  // wave-uniform
+                const int leader = __ffsll((long long)active) - 1;
+                const uint32_t lb = (uint32_t)__shfl((int)b, leader, 64);
+                const unsigned long long same = __ballot(counts && b == lb);
+                if ((int)(tid & 63u) == leader)
+                    atomicAdd(&s_bins[lb], (uint32_t)__popcll(same));
+                else if (counts && b != lb)
+                    atomicAdd(&s_bins[b], 1u);
+            }
+        } else {
+            if (counts) atomicAdd(&s_bins[b], 1u);
+        }
+    };
+    // v (not a NaN), n times: the extremes, and below / above / its bin (false: it has a bin)
+    auto classify = [&](float v, uint32_t n) __attribute__((always_inline)) {
+        const uint32_t o = ordered(v == 0.0f ? 0.0f : v);  // -0.0 orders as 0
+        inv_mn = ~o > inv_mn ? ~o : inv_mn;
+        mx = o > mx ? o : mx;
+        const bool lt = v < lo, gt = v > hi;
+        below += lt ? n : 0u;  // (unconditional adds: a choice between the two counters' addresses
+        above += gt ? n : 0u;  //  would keep them in scratch)
+        return lt || gt;
+    };
+    if constexpr (kHistCodes<VT>) {
+        const uint32_t wave = tid >> 6, lane = tid & 63u;
+        const uint32_t yl = lane % (uint32_t)G::BY, zl = lane / (uint32_t)G::BY;
+        for (uint32_t w0 = blockIdx.x * 4u; w0 < A.nwork; w0 += gridDim.x * 4u) {
+            const uint32_t w = w0 + wave;
+            if (w >= A.nwork) continue;  // wave-uniform
+            const uint32_t bx = A.b0[0] + w % A.nb[0], by = A.b0[1] + (w / A.nb[0]) % A.nb[1],
+                           bz = A.b0[2] + w / (A.nb[0] * A.nb[1]);
+            const uint32_t y = by * (uint32_t)G::BY + yl - (uint32_t)kPad,
+                           z = bz * (uint32_t)G::BZ + zl - (uint32_t)kPad;
+            const bool row_in = y >= A.box_min[1] && y < A.box_max[1] && z >= A.box_min[2] && z < A.box_max[2];
+            const V *__restrict__ row = vol + (size_t)brick_slot(bx, by, bz, A.nbx, A.nby) * (size_t)G::Elems +
+                                        (zl * (uint32_t)G::EY + yl) * (uint32_t)G::EX;
+            // (bricks are 648 B and rows 8 B: the row is 8-aligned)
+            const uint2 d = row_in ? *reinterpret_cast<const uint2 *>(row) : make_uint2(0u, 0u);
+#pragma unroll
+            for (uint32_t xl = 0; xl < (uint32_t)G::BX; ++xl) {
+                const uint32_t x = bx * (uint32_t)G::BX + xl - (uint32_t)kPad;
+                const uint32_t code = ((xl < 4 ? d.x : d.y) >> (8u * (xl & 3u))) & 0xFFu;
+                add(row_in && x >= A.box_min[0] && x < A.box_max[0], code);
+            }
+        }
+        __syncthreads();
+        // fold: thread c owns code c
+        const uint32_t n = s_bins[tid];
+        if (n) {
+            const float v = (float)(V)tid;
+            if (!classify(v, n)) atomicAdd(&out[bin_of(v)], (unsigned long long)n);
+        }
+    } else {
+        for (uint32_t w = blockIdx.x; w < A.nwork; w += gridDim.x) {
+            const uint32_t bx = A.b0[0] + w % A.nb[0], by = A.b0[1] + (w / A.nb[0]) % A.nb[1],
+                           bz = A.b0[2] + w / (A.nb[0] * A.nb[1]);
+            const V *__restrict__ src =
+                vol + (size_t)brick_slot(bx, by, bz, A.nbx, A.nby) * (size_t)G::Elems * vpe;
+#pragma unroll
+            for (uint32_t c = tid; c < kCells; c += 256) {
+                const uint32_t xl = c % (uint32_t)G::BX, yl = (c / (uint32_t)G::BX) % (uint32_t)G::BY,
+                               zl = c / (uint32_t)(G::BX * G::BY);
+                // logical index = padded - kPad; a padding cell wraps to a huge value and fails < max
+                const uint32_t x = bx * (uint32_t)G::BX + xl - (uint32_t)kPad,
+                               y = by * (uint32_t)G::BY + yl - (uint32_t)kPad,
+                               z = bz * (uint32_t)G::BZ + zl - (uint32_t)kPad;
+                const bool in = x >= A.box_min[0] && x < A.box_max[0] && y >= A.box_min[1] &&
+                                y < A.box_max[1] && z >= A.box_min[2] && z < A.box_max[2];
+                bool counts = false;
+                uint32_t b = 0;
+                if (in) {
+                    const float v = (float)src[((zl * (uint32_t)G::EY + yl) * (uint32_t)G::EX + xl) * vpe];
+                    if (v != v) {
+                        ++nan;
+                    } else if (!classify(v, 1u)) {
+                        b = bin_of(v);
+                        counts = true;
+                    }
+                }
+                add(counts, b);
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        below += __shfl_xor(below, off, 64);
+        above += __shfl_xor(above, off, 64);
+        nan += __shfl_xor(nan, off, 64);
+        const uint32_t m2 = __shfl_xor(inv_mn, off, 64), h2 = __shfl_xor(mx, off, 64);
+        inv_mn = m2 > inv_mn ? m2 : inv_mn;
+        mx = h2 > mx ? h2 : mx;
+    }
+    if ((tid & 63u) == 0) {
+        uint32_t *r = s_red[tid >> 6];
+        r[0] = below;
+        r[1] = above;
+        r[2] = nan;
+        r[3] = inv_mn;
+        r[4] = mx;
+    }
+    __syncthreads();
+    if constexpr (!kHistCodes<VT>) {
+        for (uint32_t i = tid; i < nbins; i += 256) {
+            const uint32_t n = s_bins[i];
+            if (n) atomicAdd(&out[i], (unsigned long long)n);
+        }
+    }
+    if (tid == 0) {
+        for (uint32_t i = 1; i < 4; ++i) {
+            below += s_red[i][0];
+            above += s_red[i][1];
+            nan += s_red[i][2];
+            inv_mn = s_red[i][3] > inv_mn ? s_red[i][3] : inv_mn;
+            mx = s_red[i][4] > mx ? s_red[i][4] : mx;
+        }
+        if (below) atomicAdd(&out[nbins + 0], (unsigned long long)below);
+        if (above) atomicAdd(&out[nbins + 1], (unsigned long long)above);
+        if (nan) atomicAdd(&out[nbins + 2], (unsigned long long)nan);
+        uint32_t *__restrict__ ext = reinterpret_cast<uint32_t *>(out + nbins + 3);
+        atomicMax(&ext[0], inv_mn);
+        atomicMax(&ext[1], mx);
+    }
+}
+
 // One thread per brick: 0 if the brick can produce a visible sample, kSkipCap if EMPTY.
 // Brick b is empty when every density d the trilinear filter can produce from its values maps
 // to TF texels of alpha 0.  d lies in [lo, hi] up to the filter's rounding (3 levels of fmaf
@@ -3035,6 +3226,43 @@ hipError_t launch_mpr(int layout, bool count, const MprArgs &a, hipStream_t stre
         case TAG_F32: launch_mpr_tag<float>(a, nblocks, stream); break;
         case TAG_QUAD_U8: launch_mpr_tag<Quad8<uint8_t>>(a, nblocks, stream); break;
         default: launch_mpr_tag<Quad8<int8_t>>(a, nblocks, stream); break;
+    }
+    return hipGetLastError();
+}
+
+namespace {
+template <typename VT>
+void launch_hist_tag(bool agg, const HistArgs &a, uint32_t nblocks, hipStream_t stream)
+{
+    if (agg)
+        hipLaunchKernelGGL((hist_kernel<VT, true>), dim3(nblocks), dim3(256), 0, stream, a);
+    else
+        hipLaunchKernelGGL((hist_kernel<VT, false>), dim3(nblocks), dim3(256), 0, stream, a);
+}
+}  // namespace
+
+hipError_t launch_hist(int layout, bool agg, const HistArgs &a, hipStream_t stream, std::string *name)
+{
+    const int tag = layout >= ST_U8 && layout <= ST_F32 ? layout
+                    : layout == (ST_U8 | kQuadFlag)     ? (int)TAG_QUAD_U8
+                    : layout == (ST_I8 | kQuadFlag)     ? (int)TAG_QUAD_I8
+                                                        : -1;
+    if (tag < 0 || a.nwork == 0 || a.nbins == 0 || a.nbins > kHistMaxBins) return hipErrorInvalidValue;
+    if (name)
+        *name = std::string("void vr::(anonymous namespace)::hist_kernel<") + kTagNames[tag] +
+                (agg ? ", true" : ", false") + ">(vr::HistArgs)";
+    // (the code path of plain 8-bit bricks walks a brick per wave: four per workgroup)
+    const uint32_t groups = (tag == TAG_U8 && kHistCodes<uint8_t>) || (tag == TAG_I8 && kHistCodes<int8_t>)
+                                ? (a.nwork + 3) / 4 : a.nwork;
+    const uint32_t nblocks = groups < kHistMaxGrid ? groups : kHistMaxGrid;
+    switch (tag) {
+        case TAG_U8: launch_hist_tag<uint8_t>(agg, a, nblocks, stream); break;
+        case TAG_I8: launch_hist_tag<int8_t>(agg, a, nblocks, stream); break;
+        case TAG_U16: launch_hist_tag<uint16_t>(agg, a, nblocks, stream); break;
+        case TAG_I16: launch_hist_tag<int16_t>(agg, a, nblocks, stream); break;
+        case TAG_F32: launch_hist_tag<float>(agg, a, nblocks, stream); break;
+        case TAG_QUAD_U8: launch_hist_tag<Quad8<uint8_t>>(agg, a, nblocks, stream); break;
+        default: launch_hist_tag<Quad8<int8_t>>(agg, a, nblocks, stream); break;
     }
     return hipGetLastError();
 }

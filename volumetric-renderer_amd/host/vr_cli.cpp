@@ -18,6 +18,12 @@
 //                                        of include/vr/vr_mpr.h at --size -- the plane at
 //                                        POSITION in [0,1] along the axis, thin or a slab of
 //                                        NSAMPLES samples SPACING apart -- instead of the 3D frame)
+//          [--histogram N[:LO:HI]]   (write, in place of the image, the volume's value histogram of
+//                                        include/vr/vr_hist.h as one JSON object: N bins over
+//                                        [LO, HI], by default the dataset's value window)
+//          [--window P_LO:P_HI]   (render with the value window set to the percentiles P_LO .. P_HI,
+//                                        in [0,1], of a 4096-bin histogram over the data's exact range)
+#include <cmath>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -28,13 +34,48 @@
 #include "../../include/vr/offscreen_pass_hip.hpp"
 #include "../../include/vr/vr_host.h"
 
+namespace {
+std::vector<std::string> split_colons(const std::string &s)
+{
+    std::vector<std::string> f;
+    for (size_t b = 0;;) {
+        const size_t e = s.find(':', b);
+        f.push_back(s.substr(b, e == std::string::npos ? e : e - b));
+        if (e == std::string::npos) break;
+        b = e + 1;
+    }
+    return f;
+}
+
+// the whole of s as a number
+bool parse_double(const std::string &s, double *v)
+{
+    if (s.empty()) return false;
+    char *end = nullptr;
+    *v = std::strtod(s.c_str(), &end);
+    return end && *end == '\0';
+}
+
+// %.9g, with the non-finite values spelt as JSON readers that accept them do
+void print_float(FILE *fp, float v)
+{
+    if (v != v)
+        std::fprintf(fp, "NaN");
+    else if (std::isinf(v))
+        std::fprintf(fp, v > 0 ? "Infinity" : "-Infinity");
+    else
+        std::fprintf(fp, "%.9g", (double)v);
+}
+}  // namespace
+
 int main(int argc, char **argv)
 {
     if (argc < 3) {
         std::fprintf(stderr, "usage: %s <file.nhdr|synthetic:N> <out.ppm> [--size WxH] [--radius R] "
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
                              "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V] "
-                             "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]]\n",
+                             "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]] "
+                             "[--histogram N[:LO:HI]] [--window P_LO:P_HI]\n",
                      argv[0]);
         return 2;
     }
@@ -43,7 +84,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default", mode = "composite", mpr;
+    std::string tfname = "default", mode = "composite", mpr, hist, window;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -57,6 +98,8 @@ int main(int argc, char **argv)
         else if (a == "--mode" && i + 1 < argc) mode = argv[++i];
         else if (a == "--iso" && i + 1 < argc) iso = std::strtof(argv[++i], nullptr);
         else if (a == "--mpr" && i + 1 < argc) mpr = argv[++i];
+        else if (a == "--histogram" && i + 1 < argc) hist = argv[++i];
+        else if (a == "--window" && i + 1 < argc) window = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -71,13 +114,7 @@ int main(int argc, char **argv)
     // --mpr AXIS:POSITION[:NSAMPLES:SPACING:OP]
     vr_mpr_plane plane{};
     if (!mpr.empty()) {
-        std::vector<std::string> f;
-        for (size_t b = 0;;) {
-            const size_t e = mpr.find(':', b);
-            f.push_back(mpr.substr(b, e == std::string::npos ? e : e - b));
-            if (e == std::string::npos) break;
-            b = e + 1;
-        }
+        const std::vector<std::string> f = split_colons(mpr);
         const int axis = f[0] == "sagittal" ? 0 : f[0] == "coronal" ? 1 : f[0] == "axial" ? 2 : -1;
         const int op = f.size() == 5 ? (f[4] == "max" ? VR_MPR_MAX : f[4] == "min" ? VR_MPR_MIN
                                         : f[4] == "mean" ? VR_MPR_MEAN : -1)
@@ -90,6 +127,39 @@ int main(int argc, char **argv)
         const float spacing = f.size() == 5 ? std::strtof(f[3].c_str(), nullptr) : 0.0f;
         if (vr_mpr_axis_plane(axis, std::strtof(f[1].c_str(), nullptr), W, H, ns, spacing, op, &plane) != VR_OK) {
             std::fprintf(stderr, "bad --mpr %s: %s\n", mpr.c_str(), vr_last_error(nullptr));
+            return 2;
+        }
+    }
+    // --histogram N[:LO:HI]
+    uint32_t hist_bins = 0;
+    bool hist_range = false;
+    float hist_lo = 0.0f, hist_hi = 0.0f;
+    if (!hist.empty()) {
+        const std::vector<std::string> f = split_colons(hist);
+        double n = 0.0, lo = 0.0, hi = 1.0;
+        bool ok = (f.size() == 1 || f.size() == 3) && parse_double(f[0], &n) && n >= 1.0 &&
+                  n <= (double)VR_HIST_MAX_BINS && n == std::floor(n);
+        if (ok && f.size() == 3) {
+            ok = parse_double(f[1], &lo) && parse_double(f[2], &hi);
+            hist_lo = (float)lo;
+            hist_hi = (float)hi;
+            ok = ok && std::isfinite(hist_lo) && std::isfinite(hist_hi) && hist_lo < hist_hi;
+            hist_range = true;
+        }
+        if (!ok) {
+            std::fprintf(stderr, "bad --histogram %s (N[:LO:HI], 1 <= N <= %d, finite LO < HI)\n",
+                         hist.c_str(), VR_HIST_MAX_BINS);
+            return 2;
+        }
+        hist_bins = (uint32_t)n;
+    }
+    // --window P_LO:P_HI
+    double win_lo = 0.0, win_hi = 1.0;
+    if (!window.empty()) {
+        const std::vector<std::string> f = split_colons(window);
+        if (f.size() != 2 || !parse_double(f[0], &win_lo) || !parse_double(f[1], &win_hi) ||
+            !(win_lo >= 0.0 && win_lo < win_hi && win_hi <= 1.0)) {
+            std::fprintf(stderr, "bad --window %s (P_LO:P_HI, 0 <= P_LO < P_HI <= 1)\n", window.c_str());
             return 2;
         }
     }
@@ -109,6 +179,52 @@ int main(int argc, char **argv)
                                          ds.dims[2], ds.vmin, ds.vmax);
             vr_dataset_free(&ds);
             if (rc != VR_OK) throw std::runtime_error(vr_last_error(pass.handle()));
+        }
+        if (hist_bins) {  // the histogram in place of the image
+            float mm[2] = {0.0f, 1.0f};
+            if (!hist_range) {
+                vr_debug_volume_info(pass.handle(), nullptr, mm, nullptr);
+                hist_lo = mm[0];
+                hist_hi = mm[1];
+            }
+            vr_hist_info info{};
+            const std::vector<uint64_t> bins = pass.histogram(hist_bins, hist_lo, hist_hi, &info);
+            FILE *fp = std::fopen(out.c_str(), "wb");
+            if (!fp) throw std::runtime_error("cannot write " + out);
+            std::fprintf(fp, "{\"nbins\": %u, \"lo\": ", hist_bins);
+            print_float(fp, hist_lo);
+            std::fprintf(fp, ", \"hi\": ");
+            print_float(fp, hist_hi);
+            std::fprintf(fp, ", \"bins\": [");
+            for (uint32_t b = 0; b < hist_bins; ++b)
+                std::fprintf(fp, b ? ", %llu" : "%llu", (unsigned long long)bins[b]);
+            std::fprintf(fp, "], \"voxels\": %llu, \"below\": %llu, \"above\": %llu, \"nan\": %llu, \"vmin\": ",
+                         (unsigned long long)info.voxels, (unsigned long long)info.below,
+                         (unsigned long long)info.above, (unsigned long long)info.nan);
+            print_float(fp, info.vmin);
+            std::fprintf(fp, ", \"vmax\": ");
+            print_float(fp, info.vmax);
+            std::fprintf(fp, "}\n");
+            std::fclose(fp);
+            std::printf("histogram of %llu voxels in %u bins -> %s\n", (unsigned long long)info.voxels,
+                        hist_bins, out.c_str());
+            return 0;
+        }
+        if (!window.empty()) {  // the percentile window of a 4096-bin histogram over the exact range
+            float mm[2] = {0.0f, 1.0f};
+            vr_debug_volume_info(pass.handle(), nullptr, mm, nullptr);
+            vr_hist_info info{};
+            if (!(mm[0] < mm[1])) mm[0] = 0.0f, mm[1] = 1.0f;  // any range: this call is for info
+            pass.histogram(1, mm[0], mm[1], &info);
+            if (!(std::isfinite(info.vmin) && std::isfinite(info.vmax) && info.vmin < info.vmax))
+                throw std::runtime_error("--window needs a volume with more than one finite value");
+            const std::vector<uint64_t> bins = pass.histogram(VR_HIST_MAX_BINS, info.vmin, info.vmax);
+            float w0 = 0.0f, w1 = 1.0f;
+            if (vr_hist_window(bins.data(), VR_HIST_MAX_BINS, info.vmin, info.vmax, win_lo, win_hi, &w0,
+                               &w1) != VR_OK)
+                throw std::runtime_error(vr_last_error(nullptr));
+            pass.value_range_changed(w0, w1);
+            std::printf("window %.9g .. %.9g\n", (double)w0, (double)w1);
         }
         // transfer function as the UI produces it (main_window.cpp:248-257)
         vr_gradient *g = vr_gradient_create();

@@ -97,6 +97,16 @@ class vr_mpr_plane(C.Structure):  # vr_mpr.h
                 ("nsamples", C.c_uint32), ("op", C.c_int32)]
 
 
+class vr_hist_request(C.Structure):  # vr_hist.h
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("nbins", C.c_uint32),
+                ("use_box", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
+
+
+class vr_hist_info(C.Structure):  # vr_hist.h
+    _fields_ = [("voxels", C.c_uint64), ("below", C.c_uint64), ("above", C.c_uint64),
+                ("nan", C.c_uint64), ("vmin", C.c_float), ("vmax", C.c_float)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -148,14 +158,18 @@ MPR_SYMBOLS = ["vr_mpr_render", "vr_mpr_render_device", "vr_mpr_count_work", "vr
 OP_MAX, OP_MIN, OP_MEAN = 0, 1, 2
 MPR_MAX_SAMPLES = 4096
 AXIS_SAGITTAL, AXIS_CORONAL, AXIS_AXIAL = 0, 1, 2
+# include/vr/vr_hist.h: the volume's value histogram, a percentile window, the window setter
+HIST_SYMBOLS = ["vr_histogram", "vr_hist_edges", "vr_hist_window", "vr_set_value_range"]
+HIST_MAX_BINS = 4096
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
 KNOBS = {"pipeline": 1, "pair": 2, "pair_lanes": 3, "grad_field": 4, "u8_layout": 6,
-         "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10, "field_order": 11}
+         "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10, "field_order": 11,
+         "hist_agg": 12}
 KNOB_AUTO = {"pipeline": -1, "pair": -1, "pair_lanes": 0, "grad_field": -1,
              "u8_layout": -1, "tile_order": 0, "narrow": 1, "alt_geometry": -1,
-             "mip_inflight": 0, "field_order": -1}
+             "mip_inflight": 0, "field_order": -1, "hist_agg": -1}
 
 ABI_VERSION = 9  # include/vr/vr.h VR_ABI_VERSION
 _LIB = None
@@ -243,6 +257,12 @@ def lib() -> C.CDLL:
         "vr_mpr_count_work": (i32, [vp, C.POINTER(vr_mpr_plane), C.POINTER(vr_params),
                                     C.POINTER(vr_stats)]),
         "vr_mpr_axis_plane": (i32, [i32, f32, u32, u32, u32, f32, i32, C.POINTER(vr_mpr_plane)]),
+        "vr_histogram": (i32, [vp, C.POINTER(vr_hist_request), C.POINTER(C.c_uint64),
+                               C.POINTER(vr_hist_info)]),
+        "vr_hist_edges": (i32, [f32, f32, u32, C.POINTER(f32)]),
+        "vr_hist_window": (i32, [C.POINTER(C.c_uint64), u32, f32, f32, C.c_double, C.c_double,
+                                 C.POINTER(f32), C.POINTER(f32)]),
+        "vr_set_value_range": (i32, [vp, f32, f32]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
@@ -304,6 +324,28 @@ def axis_plane(axis: int, position: float, width: int, height: int, nsamples: in
     if rc != 0:
         raise ValueError(f"vr_mpr_axis_plane failed ({rc}): {lib().vr_last_error(None).decode()}")
     return pl
+
+
+def hist_edges(lo: float, hi: float, nbins: int) -> np.ndarray:
+    """vr_hist_edges: the nbins lower bin edges (float32); ValueError where the C function refuses."""
+    e = np.empty(max(int(nbins), 0) if 0 <= int(nbins) <= HIST_MAX_BINS else 0, np.float32)
+    rc = lib().vr_hist_edges(float(lo), float(hi), int(nbins) & 0xFFFFFFFF,
+                             e.ctypes.data_as(C.POINTER(C.c_float)))
+    if rc != 0:
+        raise ValueError(f"vr_hist_edges failed ({rc}): {lib().vr_last_error(None).decode()}")
+    return e
+
+
+def hist_window(bins, lo: float, hi: float, p_lo: float, p_hi: float):
+    """vr_hist_window: (vmin, vmax) as float32 of the percentile window [p_lo, p_hi] of a histogram
+    over [lo, hi]; ValueError where the C function refuses."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64)
+    v0, v1 = C.c_float(), C.c_float()
+    rc = lib().vr_hist_window(b.ctypes.data_as(C.POINTER(C.c_uint64)), b.size, float(lo), float(hi),
+                              float(p_lo), float(p_hi), C.byref(v0), C.byref(v1))
+    if rc != 0:
+        raise ValueError(f"vr_hist_window failed ({rc}): {lib().vr_last_error(None).decode()}")
+    return np.float32(v0.value), np.float32(v1.value)
 
 
 def default_params(**overrides) -> vr_params:
@@ -633,6 +675,34 @@ class OffscreenPass:
         self._check(lib().vr_mpr_render_device(self._ctx, C.byref(plane), C.byref(p),
                                                C.c_void_p(out_ptr), out_format,
                                                C.c_void_p(stream or None)), "render_mpr_device")
+
+    # -- value histogram and value window (vr_hist.h) --
+    def histogram(self, nbins: int, lo: Optional[float] = None, hi: Optional[float] = None,
+                  box=None):
+        """vr_histogram of the resident volume: (uint64 counts, info dict).  lo / hi default to
+        the context's window; box = ((x0, y0, z0), (x1, y1, z1)), half open, in voxels."""
+        if lo is None or hi is None:
+            w = self.volume_info()[1]
+            lo = w[0] if lo is None else lo
+            hi = w[1] if hi is None else hi
+        req = vr_hist_request()
+        req.lo, req.hi, req.nbins = float(lo), float(hi), int(nbins)
+        if box is not None:
+            req.use_box = 1
+            for a in range(3):
+                req.box_min[a], req.box_max[a] = int(box[0][a]), int(box[1][a])
+        bins = np.zeros(min(max(int(nbins), 1), HIST_MAX_BINS), np.uint64)
+        info = vr_hist_info()
+        self._check(lib().vr_histogram(self._ctx, C.byref(req),
+                                       bins.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(info)),
+                    "histogram")
+        return bins, {"voxels": info.voxels, "below": info.below, "above": info.above,
+                      "nan": info.nan, "vmin": np.float32(info.vmin), "vmax": np.float32(info.vmax)}
+
+    def value_range_changed(self, vmin: float, vmax: float) -> None:
+        """vr_set_value_range: a new value window for the resident voxels (no re-upload)."""
+        self._check(lib().vr_set_value_range(self._ctx, float(vmin), float(vmax)),
+                    "value_range_changed")
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
