@@ -60,6 +60,7 @@
 #include "vr_iso.h"
 #include "vr_mpr.h"
 #include "vr_hist.h"
+#include "vr_hit.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -322,6 +323,44 @@ class BasicOffscreenPass {
     // Extension (vr_hist.h): a new value window (Dataset.min / max) for the resident voxels,
     // without the re-upload volume_dataset_changed would need.
     void value_range_changed(float vmin, float vmax) { check(vr_set_value_range(ctx_, vmin, vmax)); }
+
+    // Extension (vr_hit.h): where the pixels of this camera's frame come from -- one vr_hit per
+    // pixel of the framebuffer, or of the pixel rectangle rect = {x0, y0, w, h} (row-major, top
+    // row first): the point `kind` (a vr_hit_kind) finds along the pixel's ray, its distance from
+    // the camera, the density there and the step.  Pass the kind that matches the frame shown;
+    // threshold is VR_HIT_OPACITY's.  The context's state and every frame stay as they are.
+    std::vector<vr_hit> hit_image(const Camera &camera, int kind, float threshold = 0.5f,
+                                  const uint32_t *rect = nullptr)
+    {
+        vr_camera cam{};
+        for (int i = 0; i < 16; ++i) cam.view[i] = camera.view[i];
+        for (int i = 0; i < 3; ++i) cam.position[i] = camera.position[i];
+        vr_hit_request req{};
+        req.kind = kind;
+        req.threshold = threshold;
+        req.use_rect = rect ? 1u : 0u;
+        for (int a = 0; a < 4 && rect; ++a) req.rect[a] = rect[a];
+        const uint32_t w = rect ? rect[2] : width_, h = rect ? rect[3] : height_;
+        // (a rectangle the call refuses may be of any size: the vector is sized by a valid one)
+        const bool fits = !rect || ((uint64_t)rect[0] + w <= width_ && (uint64_t)rect[1] + h <= height_);
+        std::vector<vr_hit> out(fits && w && h ? (size_t)w * h : 1u);
+        check(vr_hit_render(ctx_, &cam, &params_, &req, out.data()));
+        return out;
+    }
+    // Extension (vr_hit.h): the record of one framebuffer pixel, e.g. under a mouse click; a miss
+    // has step 0xFFFFFFFF and depth +infinity.
+    vr_hit pick(const Camera &camera, uint32_t px, uint32_t py, int kind, float threshold = 0.5f)
+    {
+        vr_camera cam{};
+        for (int i = 0; i < 16; ++i) cam.view[i] = camera.view[i];
+        for (int i = 0; i < 3; ++i) cam.position[i] = camera.position[i];
+        vr_hit_request req{};
+        req.kind = kind;
+        req.threshold = threshold;
+        vr_hit out{};
+        check(vr_pick(ctx_, &cam, &params_, &req, px, py, &out));
+        return out;
+    }
 
     const std::vector<uint32_t> &image() const { return image_; }
     vr_params &params() { return params_; }  // step, ERT, shading (reference defaults)

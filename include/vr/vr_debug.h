@@ -50,9 +50,12 @@ enum vr_knob {
                                binary16 field where the policy chose the copy), 0 the z-major
                                difference field only, 1 the y-major field on every frame that
                                reads the copy, at any volume size (same bytes)              */
-    VR_KNOB_HIST_AGG = 12     /* vr_histogram (vr_hist.h): -1 auto, 0 every lane adds to its
+    VR_KNOB_HIST_AGG = 12,    /* vr_histogram (vr_hist.h): -1 auto, 0 every lane adds to its
                                bin's LDS counter, 1 lanes that share the wave's leading bin add
                                once by their count (same counts)                            */
+    VR_KNOB_HIT_INFLIGHT = 13 /* vr_hit_render, vr_hit_render_device and vr_pick (vr_hit.h):
+                               samples of a ray whose loads are in flight together: -1 auto, 1
+                               or 2 (same records)                                          */
 };
 
 /* Per-device timing of a context (ABI 7), so that a multi-GPU frame that runs slow names its

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "vr_hist_host.h"
+#include "vr_hit_host.h"
 #include "vr_variant.h"
 
 namespace vr {
@@ -574,6 +575,31 @@ constexpr uint32_t kHistMaxGrid = 2048;
 // null): the demangled kernel name.  hipErrorInvalidValue: no such layout, or no work.
 hipError_t launch_hist(int layout, bool agg, const HistArgs &a, hipStream_t stream,
                        std::string *name);
+// ---- Hit records and picking (include/vr/vr_hit.h, hit_kernel) ----
+// What hit_kernel reads beside MarchParams (its own argument, as MipArgs and IsoArgs: MarchParams
+// keeps its size).  The MarchParams of a hit launch describes the request's rectangle -- W, H,
+// local_rows and the tile counts are the rectangle's, so strip_pixel and block_tile walk its
+// pixels -- while fw / fh stay the framebuffer's: pixel (px, py) of the rectangle casts the ray of
+// framebuffer pixel (x0 + px, y0 + py).  out: W * H records of kHitRecordBytes, row-major.
+struct HitArgs {
+    void *out;
+    unsigned long long out_bytes;  // bounds-checking debug builds
+    float threshold;               // kHitOpacity
+    float iso;                     // kHitIso: the context's isovalue
+    uint32_t x0, y0;               // the rectangle's origin in the framebuffer
+};
+// Samples of a ray the hit kernels keep in flight unless VR_KNOB_HIT_INFLIGHT says otherwise: two
+// for every kind.  Whole-frame hit images, K = 1 -> K = 2, ms (profiles/r16/hit/c3.json, c4.json;
+// tools/hit_bench.py): OPACITY 0.387 -> 0.293 and 0.898 -> 0.724, MAX 0.421 -> 0.381 and 1.130 ->
+// 1.017, MIN the same, ISO 0.374 -> 0.314 and 0.838 -> 0.735; ENTRY ends at its first sample and
+// is a tie within its round-to-round spread (0.0364 / 0.0359 and 0.0736 / 0.0736).
+constexpr int kHitDefaultInFlight(int /* kind: the same side won for each */) { return 2; }
+// The hit kernel of a base layout (a storage type, or an 8-bit one | kQuadFlag) over p's tiles in
+// tile order 3: kind a vr_hit_kind, inflight 1 or 2; count: the counting kernel (one sample in
+// flight, no record written).  *name (when not null): the demangled kernel name.
+// hipErrorInvalidValue: no such layout, kind or inflight.
+hipError_t launch_hit(int layout, int kind, bool count, int inflight, const MarchParams &p,
+                      const HitArgs &a, hipStream_t stream, std::string *name);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

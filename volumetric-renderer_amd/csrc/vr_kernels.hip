@@ -2118,6 +2118,225 @@ __global__ __launch_bounds__(kThreadsPerTile) void iso_kernel(const MarchParams 
     write_tile_cost(P, tile_x, tile_y, wg_start);
 }
 
+// ---- hit records and picking (include/vr/vr_hit.h) --------------------------------------------
+// The same ray as march_strip, proj_strip and iso_strip, but the lane writes where its pixel
+// comes from instead of a colour: one 24-byte record {pos[3], depth, value, step}.  P describes
+// the request's rectangle (W, H, local_rows and the tile counts; vr_internal.h HitArgs) and the
+// ray is the one of framebuffer pixel (A.x0 + px, A.y0 + gy).  The walk is iso_strip's search
+// loop without range skipping: K steps' loads are issued before any is filtered, lanes whose
+// ray has ended or whose sample is off-slab load element 0, and the samples of a batch are
+// examined in step order behind a position cursor that repeats the ray's own additions, so the
+// record is the same for every K: OPACITY's product and "the first one wins" both need the
+// order, and what a batch loaded beyond the hit is dropped.
+//   kHitEntry    the first in-slab sample (its value may be NaN)
+//   kHitOpacity  T = T * (1 - tf(t).a) per in-slab sample with the composite's division and
+//                lookup (the TF staged in LDS and read through the LdsF4-typed pointer, or the
+//                global one when it does not fit: never a generic pointer, see tf_lookup); the
+//                first sample with (1 - T) >= threshold
+//   kHitMax      the first sample equal to the ray's maximum: d > m from -INFINITY, so a NaN and
+//   kHitMin      a -inf sample never update; the mirror image from +INFINITY.  The whole ray.
+//   kHitIso      iso_strip's search and four bisection fetches, then one fetch of the value at
+//                the refined point (a cap: the sample's own cell again, the same bits)
+// depth: once per pixel in f64, left to right, rounded to f32 once.  The record goes out as three
+// 8-byte vector stores.
+// COUNT (K = 1, so the hit ends the lane before its next step is counted): rays, steps and
+// samples up to and including the ones that ended the walk; shaded = pixels with a hit; the
+// bisection and value fetches are not counted; no record is written.
+template <typename VT, int KIND, bool COUNT, int K>
+__device__ __forceinline__ void hit_strip(const MarchParams &P, const HitArgs &A, LdsF4 *s_tf,
+                                          bool tf_in_lds, uint32_t tile_x, uint32_t tile_y,
+                                          uint32_t wave, uint32_t lane)
+{
+    static_assert(KIND >= kHitEntry && KIND <= kHitIso, "vr_hit_kind");
+    static_assert(K == 1 || K == 2, "one or two samples in flight");
+    static_assert(!COUNT || K == 1, "the counting kernels walk one step at a time");
+    constexpr bool ENTRY = KIND == kHitEntry, OPAC = KIND == kHitOpacity, MAX = KIND == kHitMax,
+                   MIN = KIND == kHitMin, ISO = KIND == kHitIso;
+    constexpr bool EXTREME = MAX || MIN;  // no early end: the whole ray
+    const LanePixel pix = strip_pixel(P, tile_x, tile_y, wave, lane);
+
+    float tex[3] = {0.f, 0.f, 0.f}, dir[3] = {0.f, 0.f, 0.f};
+    const bool covered = pix.active && pixel_ray(P, A.x0 + pix.px, A.y0 + pix.gy, tex, dir);
+
+    bool hit = false, prev = false;
+    float q0 = 0.f, q1 = 0.f, q2 = 0.f;  // ISO: the last in-slab position below the isovalue
+    float h0 = 0.f, h1 = 0.f, h2 = 0.f;  // the hit
+    float hv = 0.f;                      // its value
+    int hk = -1;                         // and its step
+    float m = MAX ? -INFINITY : INFINITY;
+    float T = 1.0f;
+    unsigned long long n_samples = 0, n_steps = 0;
+    const char *__restrict__ vol = static_cast<const char *>(P.vol);
+    const int nsteps = covered ? P.nsteps : 0;
+    float p0 = tex[0], p1 = tex[1], p2 = tex[2];
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const int kin = (covered && P.slab_default) ? interior_steps(tex, dir, P.step, nsteps) : 0;
+
+    struct Stage {
+        MipRaw<VT> r;
+        float ax, ay, az;
+        bool live, slab;
+    };
+    bool live = nsteps > 0;
+    for (int it = 0; live; it += K) {
+        Stage S[K];
+        float c0 = p0, c1 = p1, c2 = p2;  // the position of the step being examined
+#pragma unroll
+        for (int s = 0; s < K; ++s) {
+            const int k = it + s;
+            const bool interior = (unsigned)(k - 1) < (unsigned)kin;
+            // volume.frag:34-37: the first position outside ends the ray
+            live = live && k < nsteps &&
+                   (interior || !(p0 > 1.0f || p1 > 1.0f || p2 > 1.0f || p0 < 0.0f || p1 < 0.0f ||
+                                  p2 < 0.0f));
+            if (COUNT && live) ++n_steps;
+            // volume.frag:39-40 (strict)
+            const bool slab = live && (interior || (p0 < P.smax[0] && p1 < P.smax[1] &&
+                                                    p2 < P.smax[2] && p0 > P.smin[0] &&
+                                                    p1 > P.smin[1] && p2 > P.smin[2]));
+            if (COUNT && slab) ++n_samples;
+            int i, j, kk;
+            texel_coord(p0, P.fnx, i, S[s].ax);
+            texel_coord(p1, P.fny, j, S[s].ay);
+            texel_coord(p2, P.fnz, kk, S[s].az);
+            S[s].live = live;
+            S[s].slab = slab;
+            // in the cube: i in [-1, n - 1], padded index in [1, n + 1] (vr_internal.h bricks_for)
+            size_t ce = slab ? cell_offset<VT>(i + kPad, j + kPad, kk + kPad, P.nbx, P.nby) : (size_t)0;
+            if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+            S[s].r.issue(vol, ce);
+            // volume.frag:47
+            p0 = p0 + d0 * P.step;
+            p1 = p1 + d1 * P.step;
+            p2 = p2 + d2 * P.step;
+        }
+#pragma unroll
+        for (int s = 0; s < K; ++s) {  // in step order: the first hit wins
+            Cell8<VT> c;
+            S[s].r.decode(c);
+            const float d = c.tri(S[s].ax, S[s].ay, S[s].az);
+            if ((EXTREME || !hit) && S[s].live) {
+                if (S[s].slab) {
+                    bool take;
+                    if constexpr (ENTRY) {
+                        take = true;
+                    } else if constexpr (OPAC) {
+                        // volume.frag:42 and :45 (the composite's division, lookup and product)
+                        const float tt = div_by_range(d - P.vmin, P);
+                        const float4 sm = tf_in_lds ? tf_lookup(s_tf, P.tf_n, P.tf_nf, tt)
+                                                    : tf_lookup(P.tf, P.tf_n, P.tf_nf, tt);
+                        T = T * (1.0f - sm.w);
+                        take = (1.0f - T) >= A.threshold;
+                    } else if constexpr (MAX) {
+                        take = d > m;  // a NaN sample never updates
+                    } else if constexpr (MIN) {
+                        take = d < m;
+                    } else {
+                        take = d >= A.iso;  // a NaN sample never hits
+                    }
+                    if (take) {
+                        hit = true;
+                        m = d;
+                        hv = d;
+                        hk = it + s;
+                        h0 = c0;
+                        h1 = c1;
+                        h2 = c2;
+                    } else if (ISO) {
+                        prev = true;
+                        q0 = c0;
+                        q1 = c1;
+                        q2 = c2;
+                    }
+                } else if (ISO) {
+                    prev = false;
+                }
+            }
+            c0 = c0 + d0 * P.step;
+            c1 = c1 + d1 * P.step;
+            c2 = c2 + d2 * P.step;
+        }
+        if (!EXTREME) live = live && !hit;
+    }
+
+    if (COUNT) {
+        flush_counters(P, lane, covered, n_samples, hit ? 1ull : 0ull, n_steps, 0);
+        return;
+    }
+    if (!pix.active) return;
+
+    if (ISO && hit) {
+        if (prev) {  // bisection between q (below) and the hit (at or above): in-slab by convexity
+#pragma unroll 1
+            for (int r = 0; r < 4; ++r) {
+                const float m0 = (q0 + h0) * 0.5f, m1 = (q1 + h1) * 0.5f, m2 = (q2 + h2) * 0.5f;
+                int i, j, kk;
+                float ax, ay, az;
+                texel_coord(m0, P.fnx, i, ax);
+                texel_coord(m1, P.fny, j, ay);
+                texel_coord(m2, P.fnz, kk, az);
+                size_t ce = cell_offset<VT>(i + kPad, j + kPad, kk + kPad, P.nbx, P.nby);
+                if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+                Cell8<VT> c;
+                c.load(vol, ce);
+                const bool above = c.tri(ax, ay, az) >= A.iso;
+                h0 = above ? m0 : h0;
+                h1 = above ? m1 : h1;
+                h2 = above ? m2 : h2;
+                q0 = above ? q0 : m0;
+                q1 = above ? q1 : m1;
+                q2 = above ? q2 : m2;
+            }
+        }
+        int i, j, kk;
+        float ax, ay, az;
+        texel_coord(h0, P.fnx, i, ax);
+        texel_coord(h1, P.fny, j, ay);
+        texel_coord(h2, P.fnz, kk, az);
+        size_t ce = cell_offset<VT>(i + kPad, j + kPad, kk + kPad, P.nbx, P.nby);
+        if (VR_OOB(2, ce * kElemBytes<VT>, P.vol_bytes)) ce = 0;
+        Cell8<VT> c;
+        c.load(vol, ce);
+        hv = c.tri(ax, ay, az);
+    }
+
+    // the miss record: {0, 0, 0, +INFINITY, 0, 0xFFFFFFFF}
+    float depth = INFINITY;
+    if (hit) {
+        const double dx = ((double)h0 - 0.5) - (double)P.cam[0];
+        const double dy = ((double)h1 - 0.5) - (double)P.cam[1];
+        const double dz = ((double)h2 - 0.5) - (double)P.cam[2];
+        depth = (float)sqrt(dx * dx + dy * dy + dz * dz);
+    } else {
+        h0 = h1 = h2 = hv = 0.0f;
+    }
+    const size_t idx = (size_t)pix.ly * P.W + pix.px;
+    if (VR_OOB(4, idx * kHitRecordBytes + (kHitRecordBytes - 1), A.out_bytes)) return;
+    float2 *o = reinterpret_cast<float2 *>(static_cast<char *>(A.out) + idx * kHitRecordBytes);
+    o[0] = make_float2(h0, h1);
+    o[1] = make_float2(h2, depth);
+    o[2] = make_float2(hv, __uint_as_float((uint32_t)hk));
+}
+
+template <typename VT, int KIND, bool COUNT, int K>
+__global__ __launch_bounds__(kThreadsPerTile) void hit_kernel(const MarchParams P, const HitArgs A)
+{
+    const int tid = threadIdx.x;
+    uint32_t tile_x, tile_y;
+    if (!block_tile(P, tile_x, tile_y)) return;
+    if constexpr (KIND == kHitOpacity) {
+        __shared__ float4 s_tf[kTfLut];  // as march_kernel's
+        const bool tf_in_lds = P.tf_n <= kTfLds;
+        if (tf_in_lds) stage_tf(P, s_tf, (int)kThreadsPerTile);
+        __syncthreads();
+        hit_strip<VT, KIND, COUNT, K>(P, A, (LdsF4 *)s_tf, tf_in_lds, tile_x, tile_y,
+                                      (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    } else {
+        hit_strip<VT, KIND, COUNT, K>(P, A, (LdsF4 *)nullptr, false, tile_x, tile_y,
+                                      (uint32_t)tid >> 6, (uint32_t)tid & 63u);
+    }
+}
+
 // ---- lane-pair march (small launches) ----------------------------------------------------------
 // Two lanes per ray: lane 0 of the pair fetches, filters and shades the even samples, lane 1 the
 // odd ones; both keep the ray position with the same float additions (p_(k+1) = p_k + d step,
@@ -3263,6 +3482,65 @@ hipError_t launch_hist(int layout, bool agg, const HistArgs &a, hipStream_t stre
         case TAG_F32: launch_hist_tag<float>(agg, a, nblocks, stream); break;
         case TAG_QUAD_U8: launch_hist_tag<Quad8<uint8_t>>(agg, a, nblocks, stream); break;
         default: launch_hist_tag<Quad8<int8_t>>(agg, a, nblocks, stream); break;
+    }
+    return hipGetLastError();
+}
+
+namespace {
+template <typename VT, int KIND>
+void launch_hit_kind(bool count, int inflight, const MarchParams &p, const HitArgs &a, uint32_t nblocks,
+                     hipStream_t stream)
+{
+    const dim3 grid(nblocks), block(kThreadsPerTile);
+    if (count)
+        hipLaunchKernelGGL((hit_kernel<VT, KIND, true, 1>), grid, block, 0, stream, p, a);
+    else if (inflight == 2)
+        hipLaunchKernelGGL((hit_kernel<VT, KIND, false, 2>), grid, block, 0, stream, p, a);
+    else
+        hipLaunchKernelGGL((hit_kernel<VT, KIND, false, 1>), grid, block, 0, stream, p, a);
+}
+template <typename VT>
+void launch_hit_tag(int kind, bool count, int inflight, const MarchParams &p, const HitArgs &a,
+                    uint32_t nblocks, hipStream_t stream)
+{
+    switch (kind) {
+        case kHitEntry: launch_hit_kind<VT, kHitEntry>(count, inflight, p, a, nblocks, stream); break;
+        case kHitOpacity: launch_hit_kind<VT, kHitOpacity>(count, inflight, p, a, nblocks, stream); break;
+        case kHitMax: launch_hit_kind<VT, kHitMax>(count, inflight, p, a, nblocks, stream); break;
+        case kHitMin: launch_hit_kind<VT, kHitMin>(count, inflight, p, a, nblocks, stream); break;
+        default: launch_hit_kind<VT, kHitIso>(count, inflight, p, a, nblocks, stream); break;
+    }
+}
+}  // namespace
+
+hipError_t launch_hit(int layout, int kind, bool count, int inflight, const MarchParams &p,
+                      const HitArgs &a, hipStream_t stream, std::string *name)
+{
+    const int tag = layout >= ST_U8 && layout <= ST_F32 ? layout
+                    : layout == (ST_U8 | kQuadFlag)     ? (int)TAG_QUAD_U8
+                    : layout == (ST_I8 | kQuadFlag)     ? (int)TAG_QUAD_I8
+                                                        : -1;
+    if (count) inflight = 1;
+    if (tag < 0 || kind < 0 || kind >= kHitKinds || (inflight != 1 && inflight != 2) ||
+        p.tile_order != 3 || p.tile_perm)
+        return hipErrorInvalidValue;
+    if (name)
+        *name = std::string("void vr::(anonymous namespace)::hit_kernel<") + kTagNames[tag] + ", " +
+                std::to_string(kind) + (count ? ", true, " : ", false, ") + std::to_string(inflight) +
+                ">(vr::MarchParams, vr::HitArgs)";
+    if (p.tiles_x * p.tiles_y == 0) return hipSuccess;
+    // order 3: whole super-tiles, dealt over the 8 XCDs (launch_frame's grid)
+    const unsigned long long padded = ((p.supers_total + 7ull) / 8) * 8 * kSuper * kSuper;
+    if (padded >= 1ull << 31) return hipErrorInvalidValue;
+    const uint32_t nblocks = (uint32_t)padded;
+    switch (tag) {
+        case TAG_U8: launch_hit_tag<uint8_t>(kind, count, inflight, p, a, nblocks, stream); break;
+        case TAG_I8: launch_hit_tag<int8_t>(kind, count, inflight, p, a, nblocks, stream); break;
+        case TAG_U16: launch_hit_tag<uint16_t>(kind, count, inflight, p, a, nblocks, stream); break;
+        case TAG_I16: launch_hit_tag<int16_t>(kind, count, inflight, p, a, nblocks, stream); break;
+        case TAG_F32: launch_hit_tag<float>(kind, count, inflight, p, a, nblocks, stream); break;
+        case TAG_QUAD_U8: launch_hit_tag<Quad8<uint8_t>>(kind, count, inflight, p, a, nblocks, stream); break;
+        default: launch_hit_tag<Quad8<int8_t>>(kind, count, inflight, p, a, nblocks, stream); break;
     }
     return hipGetLastError();
 }

@@ -23,6 +23,11 @@
 //                                        [LO, HI], by default the dataset's value window)
 //          [--window P_LO:P_HI]   (render with the value window set to the percentiles P_LO .. P_HI,
 //                                        in [0,1], of a 4096-bin histogram over the data's exact range)
+//          [--pick X,Y --hit KIND[:THRESHOLD]]   (in place of the image, print the hit record of
+//                                        framebuffer pixel (X, Y) of this camera's frame,
+//                                        include/vr/vr_hit.h, as one JSON line: pos, depth, value
+//                                        and step, -1 for a miss.  KIND entry|opacity|max|min|iso;
+//                                        THRESHOLD is opacity's, default 0.5; iso reads --iso)
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -75,7 +80,8 @@ int main(int argc, char **argv)
                              "[--rotate DX,DY] [--tf default|demo] [--shading] [--exact-gradient] [--ert EPS] [--skip-empty] "
                              "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V] "
                              "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]] "
-                             "[--histogram N[:LO:HI]] [--window P_LO:P_HI]\n",
+                             "[--histogram N[:LO:HI]] [--window P_LO:P_HI] "
+                             "[--pick X,Y --hit entry|opacity|max|min|iso[:THRESHOLD]]\n",
                      argv[0]);
         return 2;
     }
@@ -84,7 +90,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default", mode = "composite", mpr, hist, window;
+    std::string tfname = "default", mode = "composite", mpr, hist, window, pick, hit;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -100,6 +106,8 @@ int main(int argc, char **argv)
         else if (a == "--mpr" && i + 1 < argc) mpr = argv[++i];
         else if (a == "--histogram" && i + 1 < argc) hist = argv[++i];
         else if (a == "--window" && i + 1 < argc) window = argv[++i];
+        else if (a == "--pick" && i + 1 < argc) pick = argv[++i];
+        else if (a == "--hit" && i + 1 < argc) hit = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -162,6 +170,27 @@ int main(int argc, char **argv)
             std::fprintf(stderr, "bad --window %s (P_LO:P_HI, 0 <= P_LO < P_HI <= 1)\n", window.c_str());
             return 2;
         }
+    }
+    // --pick X,Y --hit KIND[:THRESHOLD]
+    uint32_t pick_x = 0, pick_y = 0;
+    int hit_kind = -1;
+    float hit_threshold = 0.5f;
+    if (!pick.empty() || !hit.empty()) {
+        const std::vector<std::string> f = split_colons(hit);
+        hit_kind = f[0] == "entry" ? VR_HIT_ENTRY : f[0] == "opacity" ? VR_HIT_OPACITY
+                   : f[0] == "max" ? VR_HIT_MAX : f[0] == "min" ? VR_HIT_MIN
+                   : f[0] == "iso" ? VR_HIT_ISO : -1;
+        double th = 0.5;
+        char tail = 0;
+        const bool ok = hit_kind >= 0 && f.size() <= 2 && (f.size() == 1 || parse_double(f[1], &th)) &&
+                        th > 0.0 && th <= 1.0 &&
+                        std::sscanf(pick.c_str(), "%u,%u%c", &pick_x, &pick_y, &tail) == 2;
+        if (!ok) {
+            std::fprintf(stderr, "bad --pick %s --hit %s (X,Y and entry|opacity|max|min|iso[:THRESHOLD], "
+                                 "0 < THRESHOLD <= 1)\n", pick.c_str(), hit.c_str());
+            return 2;
+        }
+        hit_threshold = (float)th;
     }
     try {
         Vol::Rendering::Hip::OffscreenPass pass = mask ? Vol::Rendering::Hip::OffscreenPass(
@@ -257,6 +286,21 @@ int main(int argc, char **argv)
         pass.params().exact_gradient = exact_gradient;
         pass.params().skip_empty = skip_empty;
         pass.params().ert_eps = ert;
+
+        if (hit_kind >= 0) {  // the pixel's hit record in place of the image
+            const vr_hit h = pass.pick(cam, pick_x, pick_y, hit_kind, hit_threshold);
+            std::printf("{\"pos\": [");
+            for (int a = 0; a < 3; ++a) {
+                if (a) std::printf(", ");
+                print_float(stdout, h.pos[a]);
+            }
+            std::printf("], \"depth\": ");
+            print_float(stdout, h.depth);
+            std::printf(", \"value\": ");
+            print_float(stdout, h.value);
+            std::printf(", \"step\": %lld}\n", h.step == 0xFFFFFFFFu ? -1ll : (long long)h.step);
+            return 0;
+        }
 
         auto t0 = std::chrono::steady_clock::now();
         std::vector<uint32_t> mpr_img(mpr.empty() ? 0 : (size_t)W * H);

@@ -107,6 +107,16 @@ class vr_hist_info(C.Structure):  # vr_hist.h
                 ("nan", C.c_uint64), ("vmin", C.c_float), ("vmax", C.c_float)]
 
 
+class vr_hit_request(C.Structure):  # vr_hit.h
+    _fields_ = [("kind", C.c_int32), ("threshold", C.c_float), ("use_rect", C.c_uint32),
+                ("rect", C.c_uint32 * 4)]
+
+
+class vr_hit(C.Structure):  # vr_hit.h
+    _fields_ = [("pos", C.c_float * 3), ("depth", C.c_float), ("value", C.c_float),
+                ("step", C.c_uint32)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -161,15 +171,21 @@ AXIS_SAGITTAL, AXIS_CORONAL, AXIS_AXIAL = 0, 1, 2
 # include/vr/vr_hist.h: the volume's value histogram, a percentile window, the window setter
 HIST_SYMBOLS = ["vr_histogram", "vr_hist_edges", "vr_hist_window", "vr_set_value_range"]
 HIST_MAX_BINS = 4096
+# include/vr/vr_hit.h: per-pixel hit records of the 3D frame, picking, and enum vr_hit_kind
+HIT_SYMBOLS = ["vr_hit_render", "vr_hit_render_device", "vr_hit_count_work", "vr_pick"]
+HIT_ENTRY, HIT_OPACITY, HIT_MAX, HIT_MIN, HIT_ISO = 0, 1, 2, 3, 4
+HIT_DTYPE = np.dtype([("pos", "<f4", 3), ("depth", "<f4"), ("value", "<f4"), ("step", "<u4")])
+HIT_MISS_STEP = 0xFFFFFFFF
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
 KNOBS = {"pipeline": 1, "pair": 2, "pair_lanes": 3, "grad_field": 4, "u8_layout": 6,
          "tile_order": 7, "narrow": 8, "alt_geometry": 9, "mip_inflight": 10, "field_order": 11,
-         "hist_agg": 12}
+         "hist_agg": 12, "hit_inflight": 13}
 KNOB_AUTO = {"pipeline": -1, "pair": -1, "pair_lanes": 0, "grad_field": -1,
              "u8_layout": -1, "tile_order": 0, "narrow": 1, "alt_geometry": -1,
-             "mip_inflight": 0, "field_order": -1, "hist_agg": -1}
+             "mip_inflight": 0, "field_order": -1, "hist_agg": -1,
+             "hit_inflight": -1}
 
 ABI_VERSION = 9  # include/vr/vr.h VR_ABI_VERSION
 _LIB = None
@@ -263,6 +279,14 @@ def lib() -> C.CDLL:
         "vr_hist_window": (i32, [C.POINTER(C.c_uint64), u32, f32, f32, C.c_double, C.c_double,
                                  C.POINTER(f32), C.POINTER(f32)]),
         "vr_set_value_range": (i32, [vp, f32, f32]),
+        "vr_hit_render": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params),
+                                C.POINTER(vr_hit_request), vp]),
+        "vr_hit_render_device": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params),
+                                       C.POINTER(vr_hit_request), vp, vp]),
+        "vr_hit_count_work": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params),
+                                    C.POINTER(vr_hit_request), C.POINTER(vr_stats)]),
+        "vr_pick": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params), C.POINTER(vr_hit_request),
+                          u32, u32, C.POINTER(vr_hit)]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
@@ -324,6 +348,18 @@ def axis_plane(axis: int, position: float, width: int, height: int, nsamples: in
     if rc != 0:
         raise ValueError(f"vr_mpr_axis_plane failed ({rc}): {lib().vr_last_error(None).decode()}")
     return pl
+
+
+def hit_request(kind: int, threshold: float = 0.5, rect=None) -> vr_hit_request:
+    """A vr_hit_request: the kind, OPACITY's threshold, and the pixel rectangle (x0, y0, w, h) or
+    None for the whole framebuffer."""
+    req = vr_hit_request()
+    req.kind, req.threshold = int(kind), float(threshold)
+    if rect is not None:
+        req.use_rect = 1
+        for a in range(4):
+            req.rect[a] = int(rect[a])
+    return req
 
 
 def hist_edges(lo: float, hi: float, nbins: int) -> np.ndarray:
@@ -703,6 +739,48 @@ class OffscreenPass:
         """vr_set_value_range: a new value window for the resident voxels (no re-upload)."""
         self._check(lib().vr_set_value_range(self._ctx, float(vmin), float(vmax)),
                     "value_range_changed")
+
+    # -- hit records and picking (vr_hit.h): where a pixel of the 3D frame comes from --
+    def hit_image(self, camera, params, kind: int, threshold: float = 0.5, rect=None) -> np.ndarray:
+        """vr_hit_render: the (h, w) HIT_DTYPE records of the framebuffer, or of the pixel
+        rectangle rect = (x0, y0, w, h)."""
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        p = params if params is not None else default_params()
+        req = hit_request(kind, threshold, rect)
+        w, h = (int(rect[2]), int(rect[3])) if rect is not None else self.size
+        out = np.empty((max(h, 0), max(w, 0)), HIT_DTYPE)
+        self._check(lib().vr_hit_render(self._ctx, C.byref(cam), C.byref(p), C.byref(req),
+                                        out.ctypes.data if out.size else None), "hit_image")
+        return out
+
+    def hit_image_device(self, camera, params, kind: int, out_ptr: int, threshold: float = 0.5,
+                         rect=None, stream: int = 0):
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        p = params if params is not None else default_params()
+        req = hit_request(kind, threshold, rect)
+        self._check(lib().vr_hit_render_device(self._ctx, C.byref(cam), C.byref(p), C.byref(req),
+                                               C.c_void_p(out_ptr), C.c_void_p(stream or None)),
+                    "hit_image_device")
+
+    def pick(self, camera, params, px: int, py: int, kind: int, threshold: float = 0.5) -> np.ndarray:
+        """vr_pick: the HIT_DTYPE record (a 0-d array) of framebuffer pixel (px, py)."""
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        p = params if params is not None else default_params()
+        req = hit_request(kind, threshold, None)
+        out = vr_hit()
+        self._check(lib().vr_pick(self._ctx, C.byref(cam), C.byref(p), C.byref(req), int(px), int(py),
+                                  C.byref(out)), "pick")
+        return np.frombuffer(bytes(out), HIT_DTYPE)[0]
+
+    def hit_count_work(self, camera, params, kind: int, threshold: float = 0.5, rect=None) -> dict:
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        p = params if params is not None else default_params()
+        req = hit_request(kind, threshold, rect)
+        st = vr_stats()
+        self._check(lib().vr_hit_count_work(self._ctx, C.byref(cam), C.byref(p), C.byref(req),
+                                            C.byref(st)), "hit_count_work")
+        return dict(rays=st.rays, samples=st.samples, shaded_samples=st.shaded_samples,
+                    steps=st.steps, skipped_samples=st.skipped_samples)
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
