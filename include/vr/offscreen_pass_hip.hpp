@@ -61,6 +61,7 @@
 #include "vr_mpr.h"
 #include "vr_hist.h"
 #include "vr_hit.h"
+#include "vr_mesh.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -360,6 +361,39 @@ class BasicOffscreenPass {
         vr_hit out{};
         check(vr_pick(ctx_, &cam, &params_, &req, px, py, &out));
         return out;
+    }
+
+    // Extension (vr_mesh.h): the isosurface at `iso` (density units) as an indexed triangle mesh,
+    // extracted on the device: vertex records (texture coordinates as vr_hit.pos, outward unit
+    // normals) and three indices per triangle.  closed: the surface is capped where a face of the
+    // cube or of the voxel box [box_min, box_max) cuts it.  The context's state and every frame
+    // stay as they are; vr_host.h vr_mesh_write_ply saves the result.
+    struct Mesh {
+        std::vector<vr_mesh_vertex> vertices;
+        std::vector<uint32_t> triangles;  // 3 per triangle
+        vr_mesh_info info{};
+    };
+    Mesh extract_mesh(float iso, bool closed = true, bool normals = true, const uint32_t *box_min = nullptr,
+                      const uint32_t *box_max = nullptr)
+    {
+        vr_mesh_request req{};
+        req.iso = iso;
+        req.closed = closed ? 1u : 0u;
+        req.normals = normals ? 1u : 0u;
+        req.use_box = box_min && box_max ? 1u : 0u;
+        for (int a = 0; a < 3 && req.use_box; ++a) {
+            req.box_min[a] = box_min[a];
+            req.box_max[a] = box_max[a];
+        }
+        Mesh m;
+        check(vr_mesh_count(ctx_, &req, &m.info));
+        const uint64_t nv = m.info.vertices, nt = m.info.triangles;
+        m.vertices.resize(nv ? (size_t)nv : 1u);  // (never a NULL buffer)
+        m.triangles.resize(nt ? (size_t)nt * 3 : 3u);
+        check(vr_mesh_extract(ctx_, &req, m.vertices.data(), nv, m.triangles.data(), nt, &m.info));
+        m.vertices.resize((size_t)nv);
+        m.triangles.resize((size_t)nt * 3);
+        return m;
     }
 
     const std::vector<uint32_t> &image() const { return image_; }

@@ -78,6 +78,16 @@ int vr_nrrd_write_raw(const char *nhdr_path, const void *data, int dtype, const 
 /* CSV slices, one file per z (csv_file_parser.cpp): float data, min/max seeded at 0. */
 int vr_csv_load(const char *const *paths, size_t npaths, vr_dataset *out);
 void vr_dataset_free(vr_dataset *d);
+
+/* ---- mesh output (vr_mesh.h) ---- */
+/* A binary little-endian PLY (x y z nx ny nz per vertex, a uchar-counted uint index list per face)
+ * of nv vr_mesh_vertex records and nt triangles of three uint32_t, as vr_mesh_extract returns
+ * them.  A vertex is written at pos * scale + offset per component (f32; NULL: scale 1, offset 0)
+ * -- texture coordinates to world or voxel units --, its normal unchanged.  Pure host: no device
+ * is touched.  0, -22 for a bad argument (a NULL path, a NULL array with a count, an index >= nv;
+ * no file is written), -1 when the file cannot be written; message via vr_host_last_error(). */
+int vr_mesh_write_ply(const char *path, const void *verts, uint64_t nv, const uint32_t *tris, uint64_t nt,
+                      const float scale[3], const float offset[3]);
 const char *vr_host_last_error(void);
 
 #ifdef __cplusplus

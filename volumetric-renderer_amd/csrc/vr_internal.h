@@ -11,6 +11,7 @@
 
 #include "vr_hist_host.h"
 #include "vr_hit_host.h"
+#include "vr_mesh_host.h"
 #include "vr_variant.h"
 
 namespace vr {
@@ -600,6 +601,67 @@ constexpr int kHitDefaultInFlight(int /* kind: the same side won for each */) { 
 // hipErrorInvalidValue: no such layout, kind or inflight.
 hipError_t launch_hit(int layout, int kind, bool count, int inflight, const MarchParams &p,
                       const HitArgs &a, hipStream_t stream, std::string *name);
+// ---- Isosurface mesh (include/vr/vr_mesh.h; mesh_classify_kernel, mesh_scan_*, mesh_vertex_kernel,
+// mesh_quad_kernel) ----
+// A launch walks the "work bricks" b0 .. b0 + nb of the base layout (vr_mesh_host.h
+// mesh_brick_range), work index w = x-fastest over them; a brick's cells are numbered
+// xl + BX (yl + BY zl), at most kMeshMaskWords * 32 of them.  Per work brick the scratch holds
+//   mask  kMeshMaskWords words: bit c = cell c is an active cell of the cell set (classify)
+//   cnt   {active cells, owned qualifying edges}                                  (classify)
+//   pre   the exclusive prefix of cnt inside its chunk of kMeshChunk bricks       (scan)
+// and per chunk `chunk` holds the two chunk sums, which mesh_scan_chunks_kernel turns into their
+// exclusive prefix (64-bit: 16.8 M bricks x 1536 edges pass 2^32).  So a cell's vertex id is
+// chunk[2 (w / kMeshChunk)] + pre[w].x + popcount(mask below the cell), and a brick's first quad
+// chunk[2 (w / kMeshChunk) + 1] + pre[w].y.  out: {vertices, quads, inside voxels}, zeroed by the
+// caller (inside voxels is an atomic sum; the other two are stored by the chunk scan).
+// The emit pass re-reads the cell's corners and re-applies the box rule instead of keeping three
+// edge and three direction bits per cell: 80 B of scratch per brick instead of 464 B.
+struct MeshArgs {
+    const void *vol;        // the base bricks (layout code `layout` of the launchers)
+    uint32_t *mask;
+    uint2 *cnt, *pre;
+    unsigned long long *chunk;
+    unsigned long long *out;
+    void *verts;            // vr_mesh_vertex records (mesh_vertex_kernel)
+    uint32_t *tris;         // three indices per triangle (mesh_quad_kernel)
+    float iso;
+    float fdims[3];         // float(nx) ...
+    uint32_t dims[3];
+    uint32_t nbx, nby;      // bricks per axis (x, y) of the volume
+    uint32_t lo[3], hi[3];  // the node box N, logical voxel indices, half open
+    int32_t clo[3], chi[3]; // the cell set, logical cell indices, both ends included
+    uint32_t b0[3], nb[3];  // the work bricks: first and count per axis
+    uint32_t nwork;         // nb[0] * nb[1] * nb[2]
+    uint32_t nchunks;       // ceil(nwork / kMeshChunk)
+};
+constexpr uint32_t kMeshMaskWords = 16;
+constexpr uint32_t kMeshChunk = 1024;  // bricks one workgroup of mesh_scan_bricks_kernel scans
+// workgroups of a classify / vertex / quad launch at most, as the histogram's
+constexpr uint32_t kMeshMaxGrid = 2048;
+// Bytes of the scratch of nwork work bricks, and the sub-buffers' offsets in it (all 16-aligned).
+struct MeshScratch {
+    size_t mask, cnt, pre, chunk, out, bytes;
+};
+inline MeshScratch mesh_scratch(uint64_t nwork)
+{
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t nchunks = (size_t)((nwork + kMeshChunk - 1) / kMeshChunk);
+    MeshScratch s;
+    s.mask = 0;
+    s.cnt = up(s.mask + (size_t)nwork * kMeshMaskWords * 4);
+    s.pre = up(s.cnt + (size_t)nwork * 8);
+    s.chunk = up(s.pre + (size_t)nwork * 8);
+    s.out = up(s.chunk + nchunks * 16);
+    s.bytes = s.out + 32;
+    return s;
+}
+// The passes of a base layout (a storage type, or an 8-bit one | kQuadFlag), each asynchronous on
+// `stream`.  launch_mesh_classify: classify, then the two scans, so a.out then holds the counts;
+// *name (when not null): the classify kernel's demangled name.  hipErrorInvalidValue: no such
+// layout, or no work.
+hipError_t launch_mesh_classify(int layout, const MeshArgs &a, hipStream_t stream, std::string *name);
+hipError_t launch_mesh_vertices(int layout, bool normals, const MeshArgs &a, hipStream_t stream);
+hipError_t launch_mesh_quads(int layout, const MeshArgs &a, hipStream_t stream);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

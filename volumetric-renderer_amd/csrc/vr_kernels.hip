@@ -3174,6 +3174,430 @@ __global__ __launch_bounds__(256) void hist_kernel(const HistArgs A)
     }
 }
 
+// ---- isosurface mesh (include/vr/vr_mesh.h) ----------------------------------------------------
+// Surface nets over the base bricks, four passes (vr_internal.h MeshArgs): classify, scan, vertex,
+// quad.  Classify, vertex and quad grid-stride over the work bricks, a brick per workgroup
+// iteration and a lane per cell, as hist_kernel walks a box's bricks.  A cell's eight corners are
+// its own brick's elements (Cell8's loads, apron included), so no pass looks into a neighbour
+// brick for values; the quad pass looks up neighbour cells' vertex ids, through the masks.
+// Everything a result depends on is an integer or the f32 arithmetic of one lane: no result
+// depends on an order of accumulation or on the grid.
+
+// One cell after the box rule: corner i's value is the stored one where the node lies in N and
+// +0.0f elsewhere (the closed mesh's ring; never what the bricks hold there).
+struct MeshCell {
+    float v[8];    // index dx + 2 dy + 4 dz
+    int c[3];      // the cell's logical index (padded - kPad; -1: the ring cell below voxel 0)
+    uint32_t m8;   // bit i: corner i is inside (v >= iso; a NaN never is)
+    bool in_set;   // a cell of the cell set
+};
+
+template <typename VT>
+__device__ __forceinline__ MeshCell mesh_cell(const MeshArgs &A, const char *__restrict__ vol,
+                                              uint32_t bx, uint32_t by, uint32_t bz, uint32_t cell)
+{
+    using G = GeomOf<VT>;
+    static_assert(G::Lo == 0, "the base layouts");
+    const uint32_t xl = cell % (uint32_t)G::BX, yl = (cell / (uint32_t)G::BX) % (uint32_t)G::BY,
+                   zl = cell / (uint32_t)(G::BX * G::BY);
+    MeshCell m;
+    m.c[0] = (int)(bx * (uint32_t)G::BX + xl) - kPad;
+    m.c[1] = (int)(by * (uint32_t)G::BY + yl) - kPad;
+    m.c[2] = (int)(bz * (uint32_t)G::BZ + zl) - kPad;
+    const size_t e = (size_t)brick_slot(bx, by, bz, A.nbx, A.nby) * (size_t)G::Elems +
+                     (zl * (uint32_t)G::EY + yl) * (uint32_t)G::EX + xl;
+    Cell8<VT> c8;
+    c8.load(vol, e);
+    m.m8 = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        // a node below 0 wraps to a huge value and fails < hi
+        const uint32_t x = (uint32_t)(m.c[0] + (i & 1)), y = (uint32_t)(m.c[1] + ((i >> 1) & 1)),
+                       z = (uint32_t)(m.c[2] + (i >> 2));
+        const bool in = x >= A.lo[0] && x < A.hi[0] && y >= A.lo[1] && y < A.hi[1] && z >= A.lo[2] &&
+                        z < A.hi[2];
+        m.v[i] = in ? c8.v[i] : 0.0f;
+        m.m8 |= m.v[i] >= A.iso ? 1u << i : 0u;
+    }
+    m.in_set = m.c[0] >= A.clo[0] && m.c[0] <= A.chi[0] && m.c[1] >= A.clo[1] && m.c[1] <= A.chi[1] &&
+               m.c[2] >= A.clo[2] && m.c[2] <= A.chi[2];
+    return m;
+}
+__device__ __forceinline__ bool mesh_active(const MeshCell &m)
+{
+    return m.in_set && m.m8 != 0u && m.m8 != 0xFFu;
+}
+// Bit a: the cell owns a qualifying edge along axis a -- the lattice edge from its corner 0 to
+// corner 1 << a crosses the surface and the three other cells around it are cells of the set.
+__device__ __forceinline__ uint32_t mesh_edges(const MeshArgs &A, const MeshCell &m)
+{
+    uint32_t q = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int b = (a + 1) % 3, c = (a + 2) % 3;
+        const bool cross = ((m.m8 ^ (m.m8 >> (1 << a))) & 1u) != 0u;
+        q |= m.in_set && cross && m.c[b] > A.clo[b] && m.c[c] > A.clo[c] ? 1u << a : 0u;
+    }
+    return q;
+}
+__device__ __forceinline__ void mesh_work_brick(const MeshArgs &A, uint32_t w, uint32_t &bx, uint32_t &by,
+                                                uint32_t &bz)
+{
+    bx = A.b0[0] + w % A.nb[0];
+    by = A.b0[1] + (w / A.nb[0]) % A.nb[1];
+    bz = A.b0[2] + w / (A.nb[0] * A.nb[1]);
+}
+// Active cells of work brick w below `cell`.
+__device__ __forceinline__ uint32_t mesh_prefix(const uint32_t *__restrict__ mask, uint32_t w, uint32_t cell)
+{
+    const uint32_t *__restrict__ m = mask + (size_t)w * kMeshMaskWords;
+    const uint32_t wi = cell >> 5;
+    uint32_t n = (uint32_t)__popc(m[wi] & ((1u << (cell & 31u)) - 1u));
+    for (uint32_t i = 0; i < wi; ++i) n += (uint32_t)__popc(m[i]);
+    return n;
+}
+// The vertex id of the active cell with logical index (cx, cy, cz), a cell of the cell set.
+template <typename VT>
+__device__ __forceinline__ uint32_t mesh_vertex_id(const MeshArgs &A, int cx, int cy, int cz)
+{
+    using G = GeomOf<VT>;
+    const uint32_t px = (uint32_t)(cx + kPad), py = (uint32_t)(cy + kPad), pz = (uint32_t)(cz + kPad);
+    const uint32_t bx = px / (uint32_t)G::BX, by = py / (uint32_t)G::BY, bz = pz / (uint32_t)G::BZ;
+    const uint32_t cell = (px - bx * (uint32_t)G::BX) +
+                          (uint32_t)G::BX * ((py - by * (uint32_t)G::BY) + (uint32_t)G::BY * (pz - bz * (uint32_t)G::BZ));
+    const uint32_t w = (bx - A.b0[0]) + A.nb[0] * ((by - A.b0[1]) + A.nb[1] * (bz - A.b0[2]));
+    return (uint32_t)A.chunk[2u * (w / kMeshChunk)] + A.pre[w].x + mesh_prefix(A.mask, w, cell);
+}
+
+// Pass 1.  Per brick: the mask of active cells (a ballot per wave of 64 cells), the counts of
+// active cells and of owned qualifying edges (wave popcounts, summed through LDS: s_cnt is
+// double-buffered by the iteration's parity, so a brick costs one barrier).  The inside voxels --
+// corner 0 of every walked cell whose own index lies in N -- count per lane, then per wave and
+// workgroup, before one 64-bit atomic.
+template <typename VT>
+__global__ __launch_bounds__(256) void mesh_classify_kernel(const MeshArgs A)
+{
+    using G = GeomOf<VT>;
+    constexpr uint32_t kCells = (uint32_t)(G::BX * G::BY * G::BZ);
+    constexpr uint32_t kIters = (kCells + 255u) / 256u;
+    static_assert(kCells <= kMeshMaskWords * 32u, "a brick's cells fit its mask");
+    __shared__ uint32_t s_cnt[2][4][2];
+    __shared__ uint32_t s_in[4];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const char *__restrict__ vol = static_cast<const char *>(A.vol);
+    uint32_t inside = 0, par = 0;
+    for (uint32_t w = blockIdx.x; w < A.nwork; w += gridDim.x, par ^= 1u) {
+        uint32_t bx, by, bz;
+        mesh_work_brick(A, w, bx, by, bz);
+        uint32_t nv = 0, ne = 0;
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            bool act = false;
+            uint32_t q = 0;
+            if (cell < kCells) {
+                const MeshCell m = mesh_cell<VT>(A, vol, bx, by, bz, cell);
+                act = mesh_active(m);
+                q = mesh_edges(A, m);
+                const uint32_t x = (uint32_t)m.c[0], y = (uint32_t)m.c[1], z = (uint32_t)m.c[2];
+                const bool in = x >= A.lo[0] && x < A.hi[0] && y >= A.lo[1] && y < A.hi[1] &&
+                                z >= A.lo[2] && z < A.hi[2];
+                inside += in && (m.m8 & 1u) ? 1u : 0u;
+            }
+            const unsigned long long ba = __ballot(act);
+            nv += (uint32_t)__popcll(ba);
+            ne += (uint32_t)(__popcll(__ballot((q & 1u) != 0u)) + __popcll(__ballot((q & 2u) != 0u)) +
+                             __popcll(__ballot((q & 4u) != 0u)));
+            if (lane == 0)  // cells 64 (4 it + wave) .. + 63: words 2 (4 it + wave), + 1
+                *reinterpret_cast<uint2 *>(A.mask + (size_t)w * kMeshMaskWords + (it * 4u + wave) * 2u) =
+                    make_uint2((uint32_t)ba, (uint32_t)(ba >> 32));
+        }
+        if (lane == 0) {
+            s_cnt[par][wave][0] = nv;
+            s_cnt[par][wave][1] = ne;
+        }
+        __syncthreads();
+        if (tid == 0)
+            A.cnt[w] = make_uint2(s_cnt[par][0][0] + s_cnt[par][1][0] + s_cnt[par][2][0] + s_cnt[par][3][0],
+                                  s_cnt[par][0][1] + s_cnt[par][1][1] + s_cnt[par][2][1] + s_cnt[par][3][1]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) inside += __shfl_xor(inside, off, 64);
+    if (lane == 0) s_in[wave] = inside;
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t n = s_in[0] + s_in[1] + s_in[2] + s_in[3];
+        if (n) atomicAdd(&A.out[2], (unsigned long long)n);
+    }
+}
+
+// Pass 2a.  One workgroup per chunk of kMeshChunk bricks, four bricks per lane: the exclusive
+// prefix of cnt inside the chunk into pre (32-bit: a chunk holds at most 1024 x 1536 edges), the
+// chunk's two sums into chunk.
+__global__ __launch_bounds__(256) void mesh_scan_bricks_kernel(const MeshArgs A)
+{
+    static_assert(kMeshChunk == 1024, "256 lanes x 4 bricks");
+    __shared__ uint32_t s_tot[4][2];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t i0 = blockIdx.x * kMeshChunk + tid * 4u;
+    uint2 n[4];
+    uint32_t tv = 0, te = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        n[k] = i0 + k < A.nwork ? A.cnt[i0 + k] : make_uint2(0u, 0u);
+        tv += n[k].x;
+        te += n[k].y;
+    }
+    uint32_t sv = tv, se = te;  // inclusive over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t pv = __shfl_up(sv, off, 64), pe = __shfl_up(se, off, 64);
+        sv += (int)lane >= off ? pv : 0u;
+        se += (int)lane >= off ? pe : 0u;
+    }
+    if (lane == 63) {
+        s_tot[wave][0] = sv;
+        s_tot[wave][1] = se;
+    }
+    __syncthreads();
+    uint32_t bv = sv - tv, be = se - te;  // exclusive
+    for (uint32_t k = 0; k < wave; ++k) {
+        bv += s_tot[k][0];
+        be += s_tot[k][1];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        if (i0 + k < A.nwork) A.pre[i0 + k] = make_uint2(bv, be);
+        bv += n[k].x;
+        be += n[k].y;
+    }
+    if (tid == 255) {  // (bv, be: the chunk's sums now)
+        A.chunk[2u * blockIdx.x] = bv;
+        A.chunk[2u * blockIdx.x + 1u] = be;
+    }
+}
+
+// Pass 2b.  One workgroup: the chunk sums into their exclusive prefix, 256 chunks a round with a
+// carry, in 64 bits; the totals into out[0] (vertices) and out[1] (quads).
+__device__ __forceinline__ unsigned long long shfl_up_u64(unsigned long long v, int off)
+{
+    const uint32_t lo = __shfl_up((uint32_t)v, off, 64), hi = __shfl_up((uint32_t)(v >> 32), off, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__global__ __launch_bounds__(256) void mesh_scan_chunks_kernel(const MeshArgs A)
+{
+    __shared__ unsigned long long s_tot[2][4][2];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    unsigned long long cv = 0, ce = 0;  // the carry: the sums of the rounds before
+    uint32_t par = 0;
+    for (uint32_t g0 = 0; g0 < A.nchunks; g0 += 256u, par ^= 1u) {
+        const uint32_t g = g0 + tid;
+        const unsigned long long tv = g < A.nchunks ? A.chunk[2u * g] : 0ull,
+                                 te = g < A.nchunks ? A.chunk[2u * g + 1u] : 0ull;
+        unsigned long long sv = tv, se = te;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long pv = shfl_up_u64(sv, off), pe = shfl_up_u64(se, off);
+            sv += (int)lane >= off ? pv : 0ull;
+            se += (int)lane >= off ? pe : 0ull;
+        }
+        if (lane == 63) {
+            s_tot[par][wave][0] = sv;
+            s_tot[par][wave][1] = se;
+        }
+        __syncthreads();
+        unsigned long long bv = cv + (sv - tv), be = ce + (se - te);
+        for (uint32_t k = 0; k < wave; ++k) {
+            bv += s_tot[par][k][0];
+            be += s_tot[par][k][1];
+        }
+        if (g < A.nchunks) {
+            A.chunk[2u * g] = bv;
+            A.chunk[2u * g + 1u] = be;
+        }
+        cv += s_tot[par][0][0] + s_tot[par][1][0] + s_tot[par][2][0] + s_tot[par][3][0];
+        ce += s_tot[par][0][1] + s_tot[par][1][1] + s_tot[par][2][1] + s_tot[par][3][1];
+    }
+    if (tid == 0) {
+        A.out[0] = cv;
+        A.out[1] = ce;
+    }
+}
+
+// Voxel (x, y, z) through the sampler's border rule: component 0 of its own element (what
+// unbrick_kernel reads), +0.0f outside the volume.
+template <typename VT>
+__device__ __forceinline__ float mesh_voxel(const MeshArgs &A, const char *__restrict__ vol, int x, int y,
+                                            int z)
+{
+    constexpr size_t vpe = std::is_same<VT, float>::value ? kF32VoxelsPerElement
+                                                          : (kPlainByte<VT> ? (size_t)1 : (size_t)4);
+    if ((uint32_t)x >= A.dims[0] || (uint32_t)y >= A.dims[1] || (uint32_t)z >= A.dims[2]) return 0.0f;
+    const size_t e = cell_offset<VT>(x + kPad, y + kPad, z + kPad, A.nbx, A.nby);
+    return (float)reinterpret_cast<const Vox<VT> *>(vol)[e * vpe];
+}
+
+// Pass 3.  A lane per active cell: the vertex of vr_mesh.h, at id = the brick's base + the mask's
+// prefix.  The normal's gradient is gradient<VT, false>, the device code iso_strip shades with, at
+// the texel cell of pos; where rounding puts that cell outside [-1, n - 1] -- beyond what the
+// stencil's taps may touch -- the same differences are formed voxel by voxel under the border rule.
+template <typename VT, bool NORMALS>
+__global__ __launch_bounds__(256) void mesh_vertex_kernel(const MeshArgs A)
+{
+    using G = GeomOf<VT>;
+    constexpr uint32_t kCells = (uint32_t)(G::BX * G::BY * G::BZ);
+    constexpr uint32_t kIters = (kCells + 255u) / 256u;
+    const uint32_t tid = threadIdx.x;
+    const char *__restrict__ vol = static_cast<const char *>(A.vol);
+    const long by_stride = (long)A.nbx * G::Elems;
+    const long bz_stride = (long)A.nbx * A.nby * G::Elems;
+    const float iso = A.iso;
+    for (uint32_t w = blockIdx.x; w < A.nwork; w += gridDim.x) {
+        if (A.cnt[w].x == 0u) continue;  // (workgroup-uniform)
+        uint32_t bx, by, bz;
+        mesh_work_brick(A, w, bx, by, bz);
+        const uint32_t base = (uint32_t)A.chunk[2u * (w / kMeshChunk)] + A.pre[w].x;
+#pragma unroll 1
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            if (cell >= kCells) continue;
+            if (((A.mask[(size_t)w * kMeshMaskWords + (cell >> 5)] >> (cell & 31u)) & 1u) == 0u) continue;
+            const uint32_t id = base + mesh_prefix(A.mask, w, cell);
+            const MeshCell m = mesh_cell<VT>(A, vol, bx, by, bz, cell);
+            float s0 = 0.0f, s1 = 0.0f, s2 = 0.0f, n = 0.0f;
+#pragma unroll
+            for (int a = 0; a < 3; ++a)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    // the j-th corner with bit a clear, ascending; its partner along a
+                    const int ca = a == 0 ? 2 * j : (a == 1 ? (j & 1) | ((j >> 1) << 2) : j);
+                    const int cb = ca | (1 << a);
+                    const bool cross = (((m.m8 >> ca) ^ (m.m8 >> cb)) & 1u) != 0u;
+                    const float va = m.v[ca], vb = m.v[cb];
+                    float t = (iso - va) / (vb - va);
+                    if (!(t >= 0.0f)) t = 0.0f;
+                    if (t > 1.0f) t = 1.0f;
+                    const float p0 = a == 0 ? t : (float)(ca & 1), p1 = a == 1 ? t : (float)((ca >> 1) & 1),
+                                p2 = a == 2 ? t : (float)(ca >> 2);
+                    s0 = cross ? s0 + p0 : s0;
+                    s1 = cross ? s1 + p1 : s1;
+                    s2 = cross ? s2 + p2 : s2;
+                    n = cross ? n + 1.0f : n;
+                }
+            const float pos0 = (((float)m.c[0] + 0.5f) + s0 / n) / A.fdims[0],
+                        pos1 = (((float)m.c[1] + 0.5f) + s1 / n) / A.fdims[1],
+                        pos2 = (((float)m.c[2] + 0.5f) + s2 / n) / A.fdims[2];
+            float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
+            if constexpr (NORMALS) {
+                int i, j, k;
+                float ax, ay, az, gx, gy, gz;
+                texel_coord(pos0, A.fdims[0], i, ax);
+                texel_coord(pos1, A.fdims[1], j, ay);
+                texel_coord(pos2, A.fdims[2], k, az);
+                if (i >= -1 && i < (int)A.dims[0] && j >= -1 && j < (int)A.dims[1] && k >= -1 &&
+                    k < (int)A.dims[2]) {
+                    const int pi = i + kPad, pj = j + kPad, pk = k + kPad;
+                    const size_t ce = cell_offset<VT>(pi, pj, pk, A.nbx, A.nby);
+                    Cell8<VT> c;
+                    c.load(vol, ce);
+                    gradient<VT, false>(vol, ce, c, pi, pj, pk, A.nbx, A.nby, by_stride, bz_stride, ax, ay,
+                                        az, gx, gy, gz);
+                } else {
+                    float Dx[8], Dy[8], Dz[8];
+#pragma unroll
+                    for (int o = 0; o < 8; ++o) {
+                        const int x = i + (o & 1), y = j + ((o >> 1) & 1), z = k + (o >> 2);
+                        Dx[o] = mesh_voxel<VT>(A, vol, x + 1, y, z) - mesh_voxel<VT>(A, vol, x - 1, y, z);
+                        Dy[o] = mesh_voxel<VT>(A, vol, x, y + 1, z) - mesh_voxel<VT>(A, vol, x, y - 1, z);
+                        Dz[o] = mesh_voxel<VT>(A, vol, x, y, z + 1) - mesh_voxel<VT>(A, vol, x, y, z - 1);
+                    }
+                    grad_filter<false>(Dx, Dy, Dz, ax, ay, az, gx, gy, gz);
+                }
+                const float wx = gx * A.fdims[0], wy = gy * A.fdims[1], wz = gz * A.fdims[2];
+                const float g2 = wx * wx + wy * wy + wz * wz;
+                if (g2 > 0.0f) {
+                    const float r = inv_sqrt_ieee(g2);
+                    n0 = -(wx * r);
+                    n1 = -(wy * r);
+                    n2 = -(wz * r);
+                }
+            }
+            // (f2a, u2a below: a caller's device buffer need only be 4-aligned)
+            f2a *o = reinterpret_cast<f2a *>(static_cast<char *>(A.verts) + (size_t)id * kMeshVertexBytes);
+            o[0] = f2a{pos0, pos1};
+            o[1] = f2a{pos2, n0};
+            o[2] = f2a{n1, n2};
+        }
+    }
+}
+
+// Pass 4.  A lane per cell again; the cell re-reads its corners, so its owned qualifying edges and
+// their directions are mesh_edges' once more.  A brick's quads are numbered cell by cell, x, y, z
+// within a cell: ballots give a lane its place in the wave, LDS the waves' sums (double-buffered
+// by parity: one barrier a brick).  Six indices leave as three 8-byte stores.
+template <typename VT>
+__global__ __launch_bounds__(256) void mesh_quad_kernel(const MeshArgs A)
+{
+    using G = GeomOf<VT>;
+    constexpr uint32_t kCells = (uint32_t)(G::BX * G::BY * G::BZ);
+    constexpr uint32_t kIters = (kCells + 255u) / 256u;
+    __shared__ uint32_t s_seg[2][kIters * 4u];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const char *__restrict__ vol = static_cast<const char *>(A.vol);
+    uint32_t par = 0;
+    for (uint32_t w = blockIdx.x; w < A.nwork; w += gridDim.x) {
+        if (A.cnt[w].y == 0u) continue;  // (workgroup-uniform)
+        uint32_t bx, by, bz;
+        mesh_work_brick(A, w, bx, by, bz);
+        const unsigned long long qbase = A.chunk[2u * (w / kMeshChunk) + 1u] + A.pre[w].y;
+        uint32_t q[kIters], place[kIters];
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            q[it] = 0;
+            if (cell < kCells) {
+                const MeshCell m = mesh_cell<VT>(A, vol, bx, by, bz, cell);
+                q[it] = mesh_edges(A, m) | ((m.m8 & 1u) << 3);
+            }
+            const unsigned long long e0 = __ballot((q[it] & 1u) != 0u), e1 = __ballot((q[it] & 2u) != 0u),
+                                     e2 = __ballot((q[it] & 4u) != 0u);
+            place[it] = (uint32_t)(__popcll(e0 & lt) + __popcll(e1 & lt) + __popcll(e2 & lt));
+            if (lane == 0) s_seg[par][it * 4u + wave] = (uint32_t)(__popcll(e0) + __popcll(e1) + __popcll(e2));
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            if ((q[it] & 7u) == 0u) continue;
+            uint32_t off = place[it];
+            for (uint32_t s = 0; s < it * 4u + wave; ++s) off += s_seg[par][s];
+            const uint32_t cell = it * 256u + tid;
+            const uint32_t xl = cell % (uint32_t)G::BX, yl = (cell / (uint32_t)G::BX) % (uint32_t)G::BY,
+                           zl = cell / (uint32_t)(G::BX * G::BY);
+            const int c0 = (int)(bx * (uint32_t)G::BX + xl) - kPad, c1 = (int)(by * (uint32_t)G::BY + yl) - kPad,
+                      c2 = (int)(bz * (uint32_t)G::BZ + zl) - kPad;
+            const uint32_t v2 = mesh_vertex_id<VT>(A, c0, c1, c2);
+            const bool p_in = (q[it] & 8u) != 0u;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (((q[it] >> a) & 1u) == 0u) continue;
+                // b = (a + 1) % 3, c = (a + 2) % 3: C0 = P - e_b - e_c, C1 = P - e_c, C3 = P - e_b
+                const int b0 = a == 2, b1 = a == 0, b2 = a == 1;  // e_b
+                const int d0 = a == 1, d1 = a == 2, d2 = a == 0;  // e_c
+                const uint32_t v0 = mesh_vertex_id<VT>(A, c0 - b0 - d0, c1 - b1 - d1, c2 - b2 - d2);
+                const uint32_t v1 = mesh_vertex_id<VT>(A, c0 - d0, c1 - d1, c2 - d2);
+                const uint32_t v3 = mesh_vertex_id<VT>(A, c0 - b0, c1 - b1, c2 - b2);
+                u2a *o = reinterpret_cast<u2a *>(A.tris + (size_t)(qbase + off) * 6u);
+                o[0] = u2a{v0, p_in ? v1 : v2};
+                o[1] = u2a{p_in ? v2 : v1, v0};
+                o[2] = u2a{p_in ? v2 : v3, p_in ? v3 : v2};
+                ++off;
+            }
+        }
+        par ^= 1u;
+    }
+}
+
 // One thread per brick: 0 if the brick can produce a visible sample, kSkipCap if EMPTY.
 // Brick b is empty when every density d the trilinear filter can produce from its values maps
 // to TF texels of alpha 0.  d lies in [lo, hi] up to the filter's rounding (3 levels of fmaf
@@ -3484,6 +3908,70 @@ hipError_t launch_hist(int layout, bool agg, const HistArgs &a, hipStream_t stre
         default: launch_hist_tag<Quad8<int8_t>>(agg, a, nblocks, stream); break;
     }
     return hipGetLastError();
+}
+
+namespace {
+int mesh_tag(int layout)
+{
+    return layout >= ST_U8 && layout <= ST_F32     ? layout
+           : layout == (ST_U8 | kQuadFlag)         ? (int)TAG_QUAD_U8
+           : layout == (ST_I8 | kQuadFlag)         ? (int)TAG_QUAD_I8
+                                                   : -1;
+}
+// pass: 0 classify, 1 vertices, 2 vertices with normals, 3 quads
+template <typename VT>
+void launch_mesh_tag(int pass, const MeshArgs &a, uint32_t nblocks, hipStream_t stream)
+{
+    const dim3 grid(nblocks), block(256);
+    if (pass == 0)
+        hipLaunchKernelGGL((mesh_classify_kernel<VT>), grid, block, 0, stream, a);
+    else if (pass == 1)
+        hipLaunchKernelGGL((mesh_vertex_kernel<VT, false>), grid, block, 0, stream, a);
+    else if (pass == 2)
+        hipLaunchKernelGGL((mesh_vertex_kernel<VT, true>), grid, block, 0, stream, a);
+    else
+        hipLaunchKernelGGL((mesh_quad_kernel<VT>), grid, block, 0, stream, a);
+}
+hipError_t launch_mesh_pass(int layout, int pass, const MeshArgs &a, hipStream_t stream)
+{
+    const int tag = mesh_tag(layout);
+    if (tag < 0 || a.nwork == 0) return hipErrorInvalidValue;
+    const uint32_t nblocks = a.nwork < kMeshMaxGrid ? a.nwork : kMeshMaxGrid;
+    switch (tag) {
+        case TAG_U8: launch_mesh_tag<uint8_t>(pass, a, nblocks, stream); break;
+        case TAG_I8: launch_mesh_tag<int8_t>(pass, a, nblocks, stream); break;
+        case TAG_U16: launch_mesh_tag<uint16_t>(pass, a, nblocks, stream); break;
+        case TAG_I16: launch_mesh_tag<int16_t>(pass, a, nblocks, stream); break;
+        case TAG_F32: launch_mesh_tag<float>(pass, a, nblocks, stream); break;
+        case TAG_QUAD_U8: launch_mesh_tag<Quad8<uint8_t>>(pass, a, nblocks, stream); break;
+        default: launch_mesh_tag<Quad8<int8_t>>(pass, a, nblocks, stream); break;
+    }
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_mesh_classify(int layout, const MeshArgs &a, hipStream_t stream, std::string *name)
+{
+    const int tag = mesh_tag(layout);
+    if (tag < 0 || a.nwork == 0 || a.nchunks != (a.nwork + kMeshChunk - 1) / kMeshChunk)
+        return hipErrorInvalidValue;
+    if (name)
+        *name = std::string("void vr::(anonymous namespace)::mesh_classify_kernel<") + kTagNames[tag] +
+                ">(vr::MeshArgs)";
+    if (hipError_t e = launch_mesh_pass(layout, 0, a, stream)) return e;
+    hipLaunchKernelGGL(mesh_scan_bricks_kernel, dim3(a.nchunks), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(mesh_scan_chunks_kernel, dim3(1), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_mesh_vertices(int layout, bool normals, const MeshArgs &a, hipStream_t stream)
+{
+    return launch_mesh_pass(layout, normals ? 2 : 1, a, stream);
+}
+
+hipError_t launch_mesh_quads(int layout, const MeshArgs &a, hipStream_t stream)
+{
+    return launch_mesh_pass(layout, 3, a, stream);
 }
 
 namespace {

@@ -28,6 +28,11 @@
 //                                        include/vr/vr_hit.h, as one JSON line: pos, depth, value
 //                                        and step, -1 for a miss.  KIND entry|opacity|max|min|iso;
 //                                        THRESHOLD is opacity's, default 0.5; iso reads --iso)
+//          [--mesh OUT.ply[:open]]   (in place of the image, extract the isosurface at --iso as a
+//                                        triangle mesh, include/vr/vr_mesh.h, write it as a binary
+//                                        PLY in voxel units and print its three counts as one
+//                                        JSON line.  :open leaves the surface open where a face of
+//                                        the volume cuts it)
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -81,7 +86,7 @@ int main(int argc, char **argv)
                              "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V] "
                              "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]] "
                              "[--histogram N[:LO:HI]] [--window P_LO:P_HI] "
-                             "[--pick X,Y --hit entry|opacity|max|min|iso[:THRESHOLD]]\n",
+                             "[--pick X,Y --hit entry|opacity|max|min|iso[:THRESHOLD]] [--mesh OUT.ply[:open]]\n",
                      argv[0]);
         return 2;
     }
@@ -90,7 +95,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default", mode = "composite", mpr, hist, window, pick, hit;
+    std::string tfname = "default", mode = "composite", mpr, hist, window, pick, hit, mesh;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -108,6 +113,7 @@ int main(int argc, char **argv)
         else if (a == "--window" && i + 1 < argc) window = argv[++i];
         else if (a == "--pick" && i + 1 < argc) pick = argv[++i];
         else if (a == "--hit" && i + 1 < argc) hit = argv[++i];
+        else if (a == "--mesh" && i + 1 < argc) mesh = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -237,6 +243,26 @@ int main(int argc, char **argv)
             std::fclose(fp);
             std::printf("histogram of %llu voxels in %u bins -> %s\n", (unsigned long long)info.voxels,
                         hist_bins, out.c_str());
+            return 0;
+        }
+        if (!mesh.empty()) {  // the isosurface as a PLY in place of the image
+            bool closed = true;
+            std::string ply = mesh;
+            if (ply.size() > 5 && ply.compare(ply.size() - 5, 5, ":open") == 0) {
+                closed = false;
+                ply.resize(ply.size() - 5);
+            }
+            const auto m = pass.extract_mesh(iso, closed, true);
+            uint32_t dims[3] = {1, 1, 1};
+            vr_debug_volume_info(pass.handle(), dims, nullptr, nullptr);
+            // texture coordinates -> voxel units: voxel i's centre at i
+            const float scale[3] = {(float)dims[0], (float)dims[1], (float)dims[2]}, offset[3] = {-0.5f, -0.5f, -0.5f};
+            if (vr_mesh_write_ply(ply.c_str(), m.vertices.data(), m.info.vertices, m.triangles.data(),
+                                  m.info.triangles, scale, offset) != 0)
+                throw std::runtime_error(std::string("cannot write ") + ply + ": " + vr_host_last_error());
+            std::printf("{\"vertices\": %llu, \"triangles\": %llu, \"inside_voxels\": %llu}\n",
+                        (unsigned long long)m.info.vertices, (unsigned long long)m.info.triangles,
+                        (unsigned long long)m.info.inside_voxels);
             return 0;
         }
         if (!window.empty()) {  // the percentile window of a 4096-bin histogram over the exact range

@@ -6,6 +6,8 @@
 // (src/data/nrrd_file_parser.cpp via the build's own NRRD reader; src/data/csv_file_parser.cpp).
 #include "../../include/vr/vr_host.h"
 
+#include "../csrc/vr_mesh_host.h"
+
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -760,6 +762,15 @@ extern "C" int vr_nrrd_write_raw(const char *nhdr_path, const void *data, int dt
     const size_t w = std::fwrite(data, 1, bytes, r);
     std::fclose(r);
     return w == bytes ? 0 : herr(-1, "short write");
+}
+
+// the PLY writer itself: csrc/vr_mesh_host.h (plain C++, shared with the sanitizer harness)
+extern "C" int vr_mesh_write_ply(const char *path, const void *verts, uint64_t nv, const uint32_t *tris,
+                                 uint64_t nt, const float scale[3], const float offset[3])
+{
+    const char *m = "";
+    const int rc = vr::mesh_write_ply(path, verts, nv, tris, nt, scale, offset, &m);
+    return rc ? herr(rc, m) : 0;
 }
 
 namespace {

@@ -117,6 +117,20 @@ class vr_hit(C.Structure):  # vr_hit.h
                 ("step", C.c_uint32)]
 
 
+class vr_mesh_request(C.Structure):  # vr_mesh.h
+    _fields_ = [("iso", C.c_float), ("closed", C.c_uint32), ("normals", C.c_uint32),
+                ("use_box", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
+
+
+class vr_mesh_vertex(C.Structure):  # vr_mesh.h
+    _fields_ = [("pos", C.c_float * 3), ("normal", C.c_float * 3)]
+
+
+class vr_mesh_info(C.Structure):  # vr_mesh.h
+    _fields_ = [("vertices", C.c_uint64), ("triangles", C.c_uint64), ("inside_voxels", C.c_uint64),
+                ("reserved", C.c_uint64)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -142,7 +156,7 @@ HOST_SYMBOLS = [
     "vr_gradient_remove_color_marker", "vr_gradient_remove_alpha_marker",
     "vr_gradient_set_alpha_marker", "vr_gradient_set_color_marker", "vr_gradient_marker_count",
     "vr_gradient_sample", "vr_gradient_discretize", "vr_nrrd_load", "vr_nrrd_write_raw",
-    "vr_csv_load", "vr_dataset_free", "vr_host_last_error",
+    "vr_csv_load", "vr_dataset_free", "vr_host_last_error", "vr_mesh_write_ply",
 ]
 
 DIST_SYMBOLS = [
@@ -176,6 +190,10 @@ HIT_SYMBOLS = ["vr_hit_render", "vr_hit_render_device", "vr_hit_count_work", "vr
 HIT_ENTRY, HIT_OPACITY, HIT_MAX, HIT_MIN, HIT_ISO = 0, 1, 2, 3, 4
 HIT_DTYPE = np.dtype([("pos", "<f4", 3), ("depth", "<f4"), ("value", "<f4"), ("step", "<u4")])
 HIT_MISS_STEP = 0xFFFFFFFF
+# include/vr/vr_mesh.h: the isosurface as an indexed triangle mesh (surface nets on the device)
+MESH_SYMBOLS = ["vr_mesh_count", "vr_mesh_extract", "vr_mesh_extract_device"]
+MESH_VERTEX_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3)])
+ENOSPC = -28  # VR_ENOSPC
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -287,6 +305,13 @@ def lib() -> C.CDLL:
                                     C.POINTER(vr_hit_request), C.POINTER(vr_stats)]),
         "vr_pick": (i32, [vp, C.POINTER(vr_camera), C.POINTER(vr_params), C.POINTER(vr_hit_request),
                           u32, u32, C.POINTER(vr_hit)]),
+        "vr_mesh_write_ply": (i32, [C.c_char_p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(f32),
+                                    C.POINTER(f32)]),
+        "vr_mesh_count": (i32, [vp, C.POINTER(vr_mesh_request), C.POINTER(vr_mesh_info)]),
+        "vr_mesh_extract": (i32, [vp, C.POINTER(vr_mesh_request), vp, C.c_uint64, vp, C.c_uint64,
+                                  C.POINTER(vr_mesh_info)]),
+        "vr_mesh_extract_device": (i32, [vp, C.POINTER(vr_mesh_request), vp, C.c_uint64, vp, C.c_uint64,
+                                         C.POINTER(vr_mesh_info), vp]),
         "vr_debug_create_members": (vp, [C.POINTER(i32), i32, u32, u32, i32]),
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
@@ -360,6 +385,31 @@ def hit_request(kind: int, threshold: float = 0.5, rect=None) -> vr_hit_request:
         for a in range(4):
             req.rect[a] = int(rect[a])
     return req
+
+
+def mesh_request(iso: float, closed=True, normals=True, box=None) -> vr_mesh_request:
+    """A vr_mesh_request: the isovalue (density units), the two flags, and the voxel box
+    ((x0, y0, z0), (x1, y1, z1)), half open, or None for the whole volume."""
+    req = vr_mesh_request()
+    req.iso, req.closed, req.normals = float(iso), int(closed), int(normals)
+    if box is not None:
+        req.use_box = 1
+        for a in range(3):
+            req.box_min[a], req.box_max[a] = int(box[0][a]), int(box[1][a])
+    return req
+
+
+def write_ply(path: str, verts, tris, scale=None, offset=None) -> None:
+    """vr_mesh_write_ply: verts (MESH_VERTEX_DTYPE) and tris ((T, 3) uint32) as a binary PLY, the
+    positions at pos * scale + offset."""
+    v = np.ascontiguousarray(verts, MESH_VERTEX_DTYPE)
+    t = np.ascontiguousarray(tris, np.uint32)
+    sc = (C.c_float * 3)(*scale) if scale is not None else None
+    of = (C.c_float * 3)(*offset) if offset is not None else None
+    rc = lib().vr_mesh_write_ply(os.fsencode(path), v.ctypes.data if v.size else None, v.size,
+                                 t.ctypes.data if t.size else None, t.size // 3, sc, of)
+    if rc != 0:
+        raise RuntimeError(f"vr_mesh_write_ply failed ({rc}): {lib().vr_host_last_error().decode()}")
 
 
 def hist_edges(lo: float, hi: float, nbins: int) -> np.ndarray:
@@ -781,6 +831,48 @@ class OffscreenPass:
                                             C.byref(st)), "hit_count_work")
         return dict(rays=st.rays, samples=st.samples, shaded_samples=st.shaded_samples,
                     steps=st.steps, skipped_samples=st.skipped_samples)
+
+    # -- the isosurface as a triangle mesh (vr_mesh.h) --
+    def _mesh_request(self, iso, closed, normals, box) -> vr_mesh_request:
+        return mesh_request(self.isovalue if iso is None else iso, closed, normals, box)
+
+    @staticmethod
+    def _mesh_info(info: vr_mesh_info) -> dict:
+        return {"vertices": info.vertices, "triangles": info.triangles,
+                "inside_voxels": info.inside_voxels}
+
+    def mesh_count(self, iso: Optional[float] = None, closed=True, normals=True, box=None) -> dict:
+        """vr_mesh_count: the vertices, triangles and inside voxels of the mesh at `iso` (default:
+        the context's isovalue)."""
+        req = self._mesh_request(iso, closed, normals, box)
+        info = vr_mesh_info()
+        self._check(lib().vr_mesh_count(self._ctx, C.byref(req), C.byref(info)), "mesh_count")
+        return self._mesh_info(info)
+
+    def mesh(self, iso: Optional[float] = None, closed=True, normals=True, box=None):
+        """vr_mesh_extract: (vertices as MESH_VERTEX_DTYPE records, triangles (T, 3) uint32, info
+        dict).  Sized by vr_mesh_count first."""
+        req = self._mesh_request(iso, closed, normals, box)
+        info = vr_mesh_info()
+        self._check(lib().vr_mesh_count(self._ctx, C.byref(req), C.byref(info)), "mesh_count")
+        nv, nt = int(info.vertices), int(info.triangles)
+        verts = np.zeros(max(nv, 1), MESH_VERTEX_DTYPE)  # (never a NULL buffer)
+        tris = np.zeros((max(nt, 1), 3), np.uint32)
+        self._check(lib().vr_mesh_extract(self._ctx, C.byref(req), verts.ctypes.data, nv,
+                                          tris.ctypes.data, nt, C.byref(info)), "mesh")
+        return verts[:nv], tris[:nt], self._mesh_info(info)
+
+    def mesh_device(self, verts_ptr: int, vcap: int, tris_ptr: int, tcap: int,
+                    iso: Optional[float] = None, closed=True, normals=True, box=None,
+                    stream: int = 0) -> dict:
+        """vr_mesh_extract_device: the mesh into device memory (vcap vertex records, tcap
+        triangles) on `stream`; returns the info dict when both buffers are complete."""
+        req = self._mesh_request(iso, closed, normals, box)
+        info = vr_mesh_info()
+        self._check(lib().vr_mesh_extract_device(self._ctx, C.byref(req), C.c_void_p(verts_ptr), int(vcap),
+                                                 C.c_void_p(tris_ptr), int(tcap), C.byref(info),
+                                                 C.c_void_p(stream or None)), "mesh_device")
+        return self._mesh_info(info)
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
