@@ -62,6 +62,7 @@
 #include "vr_hist.h"
 #include "vr_hit.h"
 #include "vr_mesh.h"
+#include "vr_label.h"
 
 namespace Vol::Rendering::Hip {
 
@@ -394,6 +395,86 @@ class BasicOffscreenPass {
         m.vertices.resize((size_t)nv);
         m.triangles.resize((size_t)nt * 3);
         return m;
+    }
+
+    // Extension (vr_label.h): the connected components of the value window [lo, hi] (density
+    // units, either bound may be infinite) under 6- or 26-connectivity, labelled on the device:
+    // one label per voxel of the volume or of the voxel box [box_min, box_max) in box-linear order
+    // (0: not in the window; else 1 + the smallest index of the voxel's component) and one record
+    // per component, sorted by label.  The context's state and every frame stay as they are.
+    struct Labels {
+        std::vector<uint32_t> labels;
+        std::vector<vr_label_component> components;
+        vr_label_info info{};
+    };
+    Labels label_components(float lo, float hi, uint32_t connectivity = 6, const uint32_t *box_min = nullptr,
+                            const uint32_t *box_max = nullptr)
+    {
+        const vr_label_request req = label_request(lo, hi, connectivity, box_min, box_max);
+        Labels l;
+        // One labelling where the table has at most 65536 records: a larger one is sized by the
+        // first call's VR_ENOSPC info (complete by then) and labelled once more.  A box the library
+        // will refuse counts as no voxels here, and the call says why.
+        const uint64_t n = label_voxels(req);
+        uint64_t cap = 65536;
+        l.labels.resize(n ? (size_t)n : 1u);  // (never a NULL buffer)
+        l.components.resize((size_t)cap);
+        int rc = vr_label_components(ctx_, &req, l.labels.data(), n, l.components.data(), cap, &l.info);
+        if (rc == VR_ENOSPC && l.info.voxels == n && l.info.components > cap) {
+            cap = l.info.components;
+            l.components.resize((size_t)cap);
+            rc = vr_label_components(ctx_, &req, l.labels.data(), n, l.components.data(), cap, &l.info);
+        }
+        check(rc);
+        l.labels.resize((size_t)n);
+        l.components.resize((size_t)l.info.components);
+        return l;
+    }
+    // The component of the window that holds volume voxel `seed`: a mask byte per voxel of the
+    // volume or the box (1: the seed's component) and the component's record; all zero where the
+    // seed is not in the window.
+    struct Region {
+        std::vector<uint8_t> mask;
+        vr_label_component component{};
+    };
+    Region grow_region(const uint32_t seed[3], float lo, float hi, uint32_t connectivity = 6,
+                       const uint32_t *box_min = nullptr, const uint32_t *box_max = nullptr)
+    {
+        const vr_label_request req = label_request(lo, hi, connectivity, box_min, box_max);
+        const uint64_t n = label_voxels(req);
+        Region r;
+        r.mask.resize(n ? (size_t)n : 1u);  // (never a NULL buffer)
+        check(vr_region_grow(ctx_, &req, seed, r.mask.data(), n, &r.component));
+        r.mask.resize((size_t)n);
+        return r;
+    }
+    // The voxels of a request's box, or of the volume; 0 for a box the library refuses (empty,
+    // inverted, beyond the volume or of more than 2^32 - 1 voxels), so that no buffer is sized by it.
+    uint64_t label_voxels(const vr_label_request &req)
+    {
+        uint32_t dims[3] = {0, 0, 0};
+        check(vr_debug_volume_info(ctx_, dims, nullptr, nullptr));
+        uint64_t n = 1;
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t lo = req.use_box ? req.box_min[a] : 0u, hi = req.use_box ? req.box_max[a] : dims[a];
+            if (lo >= hi || hi > dims[a] || n > 0xFFFFFFFFull / (hi - lo)) return 0;
+            n *= hi - lo;
+        }
+        return n;
+    }
+    static vr_label_request label_request(float lo, float hi, uint32_t connectivity, const uint32_t *box_min,
+                                          const uint32_t *box_max)
+    {
+        vr_label_request req{};
+        req.lo = lo;
+        req.hi = hi;
+        req.connectivity = connectivity;
+        req.use_box = box_min && box_max ? 1u : 0u;
+        for (int a = 0; a < 3 && req.use_box; ++a) {
+            req.box_min[a] = box_min[a];
+            req.box_max[a] = box_max[a];
+        }
+        return req;
     }
 
     const std::vector<uint32_t> &image() const { return image_; }

@@ -132,6 +132,12 @@ int vr_debug_variant_name(const vr_variant_facts *facts, char *buf, size_t n);
  * frame.  A multi-device context answers for member 0; "" before any launch.  The string is
  * valid until the calling thread's next call. */
 const char *vr_debug_last_kernel_name(const vr_ctx *ctx);
+/* Kernel milliseconds of each pass of the context's last vr_label_* or vr_region_grow* call
+ * (vr_label.h), taken by events between the passes while vr_timing_enable is on: ms[0..7] = local,
+ * seam, flatten, scan, table init, accumulate, largest, region-grow mask; 0 for a pass the call did
+ * not run, all 0 with timing off.  vr_timing_read's intervals are unchanged: these split them.  A
+ * multi-device context answers for member 0.  VR_EINVAL on a NULL argument. */
+int vr_debug_label_pass_ms(const vr_ctx *ctx, float ms[8]);
 
 /* Bytes the y-major copy of an f32 volume takes now on the (first) device, 0 when absent (dense-row
  * views along y of volumes beyond the Infinity Cache read it).  It counts in

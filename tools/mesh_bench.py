@@ -107,7 +107,7 @@ def run(name, args):
         t2 = time.perf_counter()
         assert m.info == info, (m.info, info)
         res["host_path"] = dict(read_volume_ms=round((t1 - t0) * 1e3, 1), numpy_reference_ms=round((t2 - t1) * 1e3, 1),
-                                normals=0, threads=os.cpu_count())
+                                normals=0)
     rp.close()
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, f"{name}.json")

@@ -11,6 +11,7 @@
 
 #include "vr_hist_host.h"
 #include "vr_hit_host.h"
+#include "vr_label_host.h"
 #include "vr_mesh_host.h"
 #include "vr_variant.h"
 
@@ -662,6 +663,72 @@ inline MeshScratch mesh_scratch(uint64_t nwork)
 hipError_t launch_mesh_classify(int layout, const MeshArgs &a, hipStream_t stream, std::string *name);
 hipError_t launch_mesh_vertices(int layout, bool normals, const MeshArgs &a, hipStream_t stream);
 hipError_t launch_mesh_quads(int layout, const MeshArgs &a, hipStream_t stream);
+// ---- Connected components and region growing (include/vr/vr_label.h; label_local_kernel,
+// label_seam_kernel, label_flatten_kernel, label_scan_chunks_kernel, label_table_init_kernel,
+// label_accum_kernel, label_largest_kernel, label_grow_kernel) ----
+// P: one word per voxel of the box N in box-linear order, parent + 1 during the passes (0: not in)
+// and the label after label_flatten_kernel.  The root table over N, cut into words of 64 voxels and
+// chunks of kLabelChunk voxels: mask (bit i of word w: voxel 64 w + i is a root), wpre (the roots of
+// the word's chunk before the word), chunk (the chunk's roots, then -- label_scan_chunks_kernel --
+// the roots before the chunk), so the record index of the component with root r is
+// chunk[r / kLabelChunk] + wpre[r / 64] + popcount(mask[r / 64] below bit r % 64): the records come
+// out sorted by label.  out: {components, in voxels, largest (voxels << 32 | ~label), 0}, zeroed by
+// the caller.
+struct LabelArgs {
+    const void *vol;        // the base bricks (layout code `layout` of launch_label)
+    uint32_t *P;
+    unsigned long long *mask;
+    uint32_t *wpre;
+    uint32_t *chunk;
+    unsigned long long *out;
+    void *comps;            // ncomps vr_label_component records (8-aligned)
+    uint8_t *grow;          // label_grow_kernel's mask, a byte per voxel of N
+    float lo, hi;           // the window
+    uint32_t nbx, nby;      // bricks per axis (x, y) of the volume
+    uint32_t blo[3], bhi[3], ext[3];  // the box N, logical voxel indices, half open; its extents
+    uint32_t b0[3], nb[3];  // the work bricks: first and count per axis
+    uint32_t nwork;         // nb[0] * nb[1] * nb[2]
+    uint32_t nvox;          // voxels of N, at most 2^32 - 1
+    uint32_t nwords;        // ceil(nvox / 64)
+    uint32_t nchunks;       // ceil(nvox / kLabelChunk)
+    uint32_t ncomps;        // records (the table passes)
+    uint32_t seed_label;    // label_grow_kernel
+};
+constexpr uint32_t kLabelChunk = 8192;  // voxels one workgroup of label_flatten_kernel walks
+constexpr uint32_t kLabelChunkWords = kLabelChunk / 64;
+// workgroups of a local / seam / table / grow launch at most, as the histogram's
+constexpr uint32_t kLabelMaxGrid = 2048;
+// Bytes of the root table of nvox voxels, and the sub-buffers' offsets in it (all 16-aligned).
+struct LabelScratch {
+    size_t mask, wpre, chunk, out, bytes;
+};
+inline LabelScratch label_scratch(uint64_t nvox)
+{
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t nwords = (size_t)((nvox + 63) / 64), nchunks = (size_t)((nvox + kLabelChunk - 1) / kLabelChunk);
+    LabelScratch s;
+    s.mask = 0;
+    s.wpre = up(s.mask + nwords * 8);
+    s.chunk = up(s.wpre + nwords * 4);
+    s.out = up(s.chunk + nchunks * 4);
+    s.bytes = s.out + 32;
+    return s;
+}
+// The passes of a base layout (a storage type, or an 8-bit one | kQuadFlag), one kernel a call (the
+// host may record an event between two), each asynchronous on `stream`.  launch_label, pass 0 ..
+// kLabelPasses - 1: local, seam, flatten, scan; after the last a.P holds the labels and a.out the
+// components and the in voxels; *name (when not null): the local kernel's demangled name.
+// launch_label_table, pass 0 .. 2: init, accumulate and largest over a.ncomps records at a.comps (a
+// region grow runs init alone, on its single record).  launch_label_grow: the mask and record 0.
+// hipErrorInvalidValue: no such layout, connectivity or pass, or no work.
+constexpr int kLabelPasses = 4;
+// vr_debug_label_pass_ms's slots: the kernels in launch order
+enum LabelPassSlot { kLabelLocal, kLabelSeam, kLabelFlatten, kLabelScan, kLabelTableInit, kLabelAccum,
+                     kLabelLargest, kLabelGrow, kLabelPassSlots };
+hipError_t launch_label(int layout, int connectivity, int pass, const LabelArgs &a, hipStream_t stream,
+                        std::string *name);
+hipError_t launch_label_table(int pass, const LabelArgs &a, hipStream_t stream);
+hipError_t launch_label_grow(const LabelArgs &a, hipStream_t stream);
 constexpr int kMipDefaultInFlight = 2;
 // range[nbricks] = {min lo, max hi} over the non-NaN bricks of range[0 .. nbricks)
 hipError_t launch_range_max(float2 *range_dev, uint32_t nbricks, hipStream_t stream);

@@ -3598,6 +3598,580 @@ __global__ __launch_bounds__(256) void mesh_quad_kernel(const MeshArgs A)
     }
 }
 
+// ---- connected components and region growing (include/vr/vr_label.h) ---------------------------
+// A lock-free union-find over the voxels of the box N (vr_internal.h LabelArgs).  The label array P
+// is the parent array: P[l] = 0 for a voxel that is not in, else 1 + the box-linear index of a
+// voxel of the same component that is not larger than l -- l itself for a root.  The local pass
+// unites inside a brick in LDS, the seam pass across bricks through P with atomicMin, the flatten
+// pass replaces every parent by the root: the root is the component's smallest index, so P then
+// holds vr_label.h's labels.  No workgroup ever waits for another: the order of the passes comes
+// from the kernel boundaries.  Every loop is bounded: a find strictly descends (a parent is smaller
+// than its child; `p >= x` also ends it on anything else), a unite retries only with one of its two
+// roots strictly lowered, the wave rounds of the table pass are counted.
+
+// parent + 1 of voxel x, as an agent-scope relaxed atomic load: it skips this CU's L1 but is served
+// by the XCD's L2, which is not coherent with the other XCDs', so the value may be stale.  Nothing
+// rests on its freshness: correctness is the stale-parent argument below and the atomicMin, which
+// executes on the word itself and returns what it really held.
+__device__ __forceinline__ uint32_t label_load(const uint32_t *P, uint32_t x)
+{
+    return __hip_atomic_load(P + (size_t)x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The root above in-voxel x as far as this thread can see.  A stale parent is an older ancestor:
+// still a voxel of x's component, and not below the true root.
+__device__ __forceinline__ uint32_t label_find(const uint32_t *P, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = label_load(P, x) - 1u;
+        if (p >= x) return x;  // (p == x: a root)
+        x = p;
+    }
+}
+// Unite the components of in-voxels a and b.  atomicMin hangs the larger root under the smaller;
+// where the larger one was no root any more (old != hi + 1), the link to old - 1 that the minimum
+// kept or replaced must not be lost: go on uniting old - 1 with lo.  hi falls on every retry.
+__device__ __forceinline__ void label_unite(uint32_t *P, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = label_find(P, a);
+        b = label_find(P, b);
+        if (a == b) return;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const uint32_t old = atomicMin(P + (size_t)hi, lo + 1u);
+        if (old == hi + 1u) return;
+        a = old - 1u;
+        b = lo;
+    }
+}
+// The same inside a brick, on the workgroup's LDS array of cell + 1.
+__device__ __forceinline__ uint32_t label_find_lds(const uint32_t *s, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = __hip_atomic_load(s + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) - 1u;
+        if (p >= x) return x;
+        x = p;
+    }
+}
+__device__ __forceinline__ void label_unite_lds(uint32_t *s, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = label_find_lds(s, a);
+        b = label_find_lds(s, b);
+        if (a == b) return;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        const uint32_t old = atomicMin(s + hi, lo + 1u);
+        if (old == hi + 1u) return;
+        a = old - 1u;
+        b = lo;
+    }
+}
+// The 13 neighbour offsets that come before a voxel in (z, y, x) order; the first three are the
+// 6-connected ones.
+__device__ constexpr int kLabelNb[13][3] = {{-1, 0, 0},  {0, -1, 0},  {0, 0, -1}, {-1, -1, 0}, {1, -1, 0},
+                                            {-1, 0, -1}, {1, 0, -1},  {0, -1, -1}, {0, 1, -1}, {-1, -1, -1},
+                                            {1, -1, -1}, {-1, 1, -1}, {1, 1, -1}};
+
+// 26-connectivity needs few of its diagonal pairs.  Let u and v = u + d differ along two or three
+// axes, and let some other voxel w of the square or cube they span (every coordinate u's or v's) be
+// in.  w differs from each of u and v along fewer axes than they differ from each other, so by
+// induction on that number -- face pairs are always united -- u ~ w and w ~ v hold without the pair
+// (u, v).  The rule reads in flags alone, which no pass changes, so both passes may apply it, each to
+// its own pairs.  in(ax, ay, az): the voxel at u + (ax, ay, az) is in.
+template <typename F>
+__device__ __forceinline__ bool label_diagonal_redundant(const int d[3], F in)
+{
+    const int n = (d[0] != 0) + (d[1] != 0) + (d[2] != 0);
+    if (n == 2) {
+        if (d[0] == 0) return in(0, d[1], 0) || in(0, 0, d[2]);
+        if (d[1] == 0) return in(d[0], 0, 0) || in(0, 0, d[2]);
+        return in(d[0], 0, 0) || in(0, d[1], 0);
+    }
+    if (n == 3)
+        return in(d[0], 0, 0) || in(0, d[1], 0) || in(0, 0, d[2]) || in(d[0], d[1], 0) || in(d[0], 0, d[2]) ||
+               in(0, d[1], d[2]);
+    return false;
+}
+
+// Pass 1.  A workgroup per work brick (grid-stride), a lane per cell: the box rule and the window
+// give the in flags; the in cells unite with their in neighbours of the same brick in LDS (cell
+// order is (z, y, x) order, as the box-linear index: the local root is the smallest l); every
+// voxel of N in the brick then gets 1 + the box-linear index of its local root, or 0, in P.
+template <typename VT, int CONN>
+__global__ __launch_bounds__(256) void label_local_kernel(const LabelArgs A)
+{
+    using G = GeomOf<VT>;
+    using V = Vox<VT>;
+    static_assert(G::Lo == 0, "the base layouts");
+    constexpr uint32_t vpe = std::is_same<VT, float>::value ? (uint32_t)kF32VoxelsPerElement
+                                                            : (kPlainByte<VT> ? 1u : 4u);
+    constexpr uint32_t BX = (uint32_t)G::BX, BY = (uint32_t)G::BY, BZ = (uint32_t)G::BZ;
+    constexpr uint32_t kCells = BX * BY * BZ;
+    constexpr uint32_t kIters = (kCells + 255u) / 256u;
+    constexpr int kNb = CONN == 6 ? 3 : 13;
+    __shared__ uint32_t s_par[kCells];
+    const uint32_t tid = threadIdx.x;
+    const V *__restrict__ vol = static_cast<const V *>(A.vol);
+    uint32_t *__restrict__ P = A.P;
+    const float lo = A.lo, hi = A.hi;
+    for (uint32_t w = blockIdx.x; w < A.nwork; w += gridDim.x) {
+        const uint32_t bx = A.b0[0] + w % A.nb[0], by = A.b0[1] + (w / A.nb[0]) % A.nb[1],
+                       bz = A.b0[2] + w / (A.nb[0] * A.nb[1]);
+        const V *__restrict__ src = vol + (size_t)brick_slot(bx, by, bz, A.nbx, A.nby) * (size_t)G::Elems * vpe;
+        bool in_n[kIters], in[kIters];
+        uint32_t lin[kIters];
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            in_n[it] = in[it] = false;
+            lin[it] = 0;
+            if (cell < kCells) {
+                const uint32_t xl = cell % BX, yl = (cell / BX) % BY, zl = cell / (BX * BY);
+                // logical index = padded - kPad; a padding cell wraps to a huge value and fails < max
+                const uint32_t x = bx * BX + xl - (uint32_t)kPad, y = by * BY + yl - (uint32_t)kPad,
+                               z = bz * BZ + zl - (uint32_t)kPad;
+                in_n[it] = x >= A.blo[0] && x < A.bhi[0] && y >= A.blo[1] && y < A.bhi[1] && z >= A.blo[2] &&
+                           z < A.bhi[2];
+                if (in_n[it]) {
+                    const float v = (float)src[((zl * (uint32_t)G::EY + yl) * (uint32_t)G::EX + xl) * vpe];
+                    in[it] = lo <= v && v <= hi;
+                    lin[it] = (x - A.blo[0]) + A.ext[0] * ((y - A.blo[1]) + A.ext[1] * (z - A.blo[2]));
+                }
+                s_par[cell] = in[it] ? cell + 1u : 0u;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            if (!in[it]) continue;
+            const int xl = (int)(cell % BX), yl = (int)((cell / BX) % BY), zl = (int)(cell / (BX * BY));
+#pragma unroll
+            for (int k = 0; k < kNb; ++k) {
+                const int nx = xl + kLabelNb[k][0], ny = yl + kLabelNb[k][1], nz = zl + kLabelNb[k][2];
+                if (nx < 0 || nx >= (int)BX || ny < 0 || ny >= (int)BY || nz < 0) continue;
+                const uint32_t ncell = (uint32_t)nx + BX * ((uint32_t)ny + BY * (uint32_t)nz);
+                // (0 stays 0: a cell that is not in is never the target of a minimum)
+                auto is_in = [&](int cx, int cy, int cz) __attribute__((always_inline)) {
+                    return __hip_atomic_load(s_par + ((uint32_t)cx + BX * ((uint32_t)cy + BY * (uint32_t)cz)),
+                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u;
+                };
+                if (!is_in(nx, ny, nz)) continue;
+                // A diagonal pair whose square or cube (inside the brick, as both ends are) holds
+                // another in cell is joined through it by pairs that differ along fewer axes.
+                if (label_diagonal_redundant(kLabelNb[k], [&](int ax, int ay, int az) __attribute__((always_inline)) {
+                        return is_in(xl + ax, yl + ay, zl + az);
+                    }))
+                    continue;
+                label_unite_lds(s_par, cell, ncell);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t it = 0; it < kIters; ++it) {
+            const uint32_t cell = it * 256u + tid;
+            if (!in_n[it]) continue;
+            uint32_t out = 0;
+            if (in[it]) {
+                const uint32_t r = label_find_lds(s_par, cell);
+                const uint32_t dx = r % BX - cell % BX, dy = (r / BX) % BY - (cell / BX) % BY,
+                               dz = r / (BX * BY) - cell / (BX * BY);  // (differences modulo 2^32)
+                out = lin[it] + dx + A.ext[0] * (dy + A.ext[1] * dz) + 1u;
+            }
+            P[(size_t)lin[it]] = out;
+        }
+        __syncthreads();  // (s_par is the next brick's)
+    }
+}
+
+// Pass 2.  A wave per row of N (grid-stride), a lane per voxel: an in voxel unites with every in
+// neighbour before it in (z, y, x) order that lies in N and in ANOTHER brick (the same brick's were
+// united in pass 1).  It reads P alone: every load an agent-scope atomic load, every store an
+// atomicMin.
+template <int CONN, typename G>
+__global__ __launch_bounds__(256) void label_seam_kernel(const LabelArgs A)
+{
+    constexpr int BX = G::BX, BY = G::BY, BZ = G::BZ;
+    constexpr int kNb = CONN == 6 ? 3 : 13;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    const uint32_t ex = A.ext[0], ey = A.ext[1], ez = A.ext[2];
+    const uint64_t nrows = (uint64_t)ey * ez;
+    uint32_t *P = A.P;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4u + wave; r < nrows; r += (uint64_t)gridDim.x * 4u) {
+        const uint32_t yb = (uint32_t)(r % ey), zb = (uint32_t)(r / ey);
+        const int yl = (int)((yb + A.blo[1] + (uint32_t)kPad) % (uint32_t)BY),
+                  zl = (int)((zb + A.blo[2] + (uint32_t)kPad) % (uint32_t)BZ);
+        // (A lane per voxel although on most rows only the voxels on an x face have work, one in BX:
+        // walking those alone, 64 face voxels of a row at once, was measured and lost -- the seam
+        // pass of C3 under 6 took 2.14 ms against this form's figure in DESIGN.md 4.12, C4's twice
+        // as long -- 64 concurrent walks to one root instead of 8.)
+        for (uint32_t xb = lane; xb < ex; xb += 64u) {
+            const int xl = (int)((xb + A.blo[0] + (uint32_t)kPad) % (uint32_t)BX);
+            if (xl != 0 && yl != 0 && zl != 0 && (CONN == 6 || (xl != BX - 1 && yl != BY - 1))) continue;
+            const uint32_t l = xb + ex * (yb + ey * zb);
+            if (label_load(P, l) == 0u) continue;
+#pragma unroll
+            for (int k = 0; k < kNb; ++k) {
+                const int dx = kLabelNb[k][0], dy = kLabelNb[k][1], dz = kLabelNb[k][2];
+                const bool crosses = (dx < 0 && xl == 0) || (dx > 0 && xl == BX - 1) || (dy < 0 && yl == 0) ||
+                                     (dy > 0 && yl == BY - 1) || (dz < 0 && zl == 0);
+                const bool in_n = (dx >= 0 || xb > 0u) && (dx <= 0 || xb + 1u < ex) && (dy >= 0 || yb > 0u) &&
+                                  (dy <= 0 || yb + 1u < ey) && (dz >= 0 || zb > 0u);
+                if (!crosses || !in_n) continue;
+                // (index differences modulo 2^32; the voxels between two voxels of N are voxels of N)
+                auto is_in = [&](int ax, int ay, int az) __attribute__((always_inline)) {
+                    return label_load(P, l + (uint32_t)ax + ex * ((uint32_t)ay + ey * (uint32_t)az)) != 0u;
+                };
+                if (!is_in(dx, dy, dz) || label_diagonal_redundant(kLabelNb[k], is_in)) continue;
+                label_unite(P, l, l + (uint32_t)dx + ex * ((uint32_t)dy + ey * (uint32_t)dz));
+            }
+        }
+    }
+}
+
+// Pass 3.  A workgroup per chunk of kLabelChunk voxels: P[l] = 1 + the root above l (a root keeps
+// its own; writing a root over a parent leaves every concurrent find a valid ancestor), so P holds
+// the labels.  On the way the roots -- P[l] == l + 1, which this pass never changes -- become the
+// root table: a bit per voxel in 64-bit words (a ballot each), the count of the chunk's roots
+// before each word, and the chunk's count; the in voxels are counted into out[1].
+__global__ __launch_bounds__(256) void label_flatten_kernel(const LabelArgs A)
+{
+    static_assert(kLabelChunk == 8192 && kLabelChunkWords == 128, "32 rounds of 256 lanes, 128 ballots");
+    __shared__ unsigned long long s_m[kLabelChunkWords];
+    __shared__ uint32_t s_tot[4], s_in[4];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint64_t base = (uint64_t)blockIdx.x * kLabelChunk;
+    uint32_t *P = A.P;
+    uint32_t nin = 0;
+    for (uint32_t it = 0; it < 32u; ++it) {
+        const uint64_t l64 = base + it * 256u + tid;
+        bool root = false;
+        if (l64 < (uint64_t)A.nvox) {
+            const uint32_t l = (uint32_t)l64, p = label_load(P, l);
+            if (p != 0u) {
+                ++nin;
+                root = p == l + 1u;
+                if (!root) P[(size_t)l] = label_find(P, p - 1u) + 1u;
+            }
+        }
+        const unsigned long long b = __ballot(root);
+        if (lane == 0) s_m[it * 4u + wave] = b;
+    }
+    __syncthreads();
+    const unsigned long long m = tid < kLabelChunkWords ? s_m[tid] : 0ull;
+    const uint32_t cnt = (uint32_t)__popcll(m);
+    uint32_t sc = cnt;  // inclusive over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t pv = __shfl_up(sc, off, 64);
+        sc += (int)lane >= off ? pv : 0u;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nin += __shfl_xor(nin, off, 64);
+    if (lane == 63) s_tot[wave] = sc;
+    if (lane == 0) s_in[wave] = nin;
+    __syncthreads();
+    const uint32_t word = blockIdx.x * kLabelChunkWords + tid;
+    if (tid < kLabelChunkWords && word < A.nwords) {
+        A.mask[word] = m;
+        A.wpre[word] = sc - cnt + (wave ? s_tot[0] : 0u);
+    }
+    if (tid == 0) {
+        A.chunk[blockIdx.x] = s_tot[0] + s_tot[1];
+        const uint32_t n = s_in[0] + s_in[1] + s_in[2] + s_in[3];
+        if (n) atomicAdd(&A.out[1], (unsigned long long)n);
+    }
+}
+
+// Pass 4a.  One workgroup: the chunks' root counts into their exclusive prefix, 256 chunks a round
+// with a carry (at most 2^32 - 1 roots: 32 bits); the total into out[0], the components.
+__global__ __launch_bounds__(256) void label_scan_chunks_kernel(const LabelArgs A)
+{
+    __shared__ uint32_t s_tot[2][4];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    uint32_t carry = 0, par = 0;
+    for (uint32_t g0 = 0; g0 < A.nchunks; g0 += 256u, par ^= 1u) {
+        const uint32_t g = g0 + tid;
+        const uint32_t t = g < A.nchunks ? A.chunk[g] : 0u;
+        uint32_t sc = t;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t pv = __shfl_up(sc, off, 64);
+            sc += (int)lane >= off ? pv : 0u;
+        }
+        if (lane == 63) s_tot[par][wave] = sc;
+        __syncthreads();
+        uint32_t b = carry + (sc - t);
+        for (uint32_t k = 0; k < wave; ++k) b += s_tot[par][k];
+        if (g < A.nchunks) A.chunk[g] = b;
+        carry += s_tot[par][0] + s_tot[par][1] + s_tot[par][2] + s_tot[par][3];
+    }
+    if (tid == 0) A.out[0] = carry;
+}
+
+// The record (vr_label_component, 64 bytes) as the table passes address it.
+struct LabelRecord {
+    uint32_t label, reserved;
+    unsigned long long voxels;
+    uint32_t bmin[3], bmax[3];
+    unsigned long long sum[3];
+};
+static_assert(sizeof(LabelRecord) == kLabelComponentBytes, "vr_label_component");
+// What a lane, a wave or a workgroup has gathered for one label.
+struct LabelAcc {
+    uint32_t cnt, mn[3], mx[3];
+    unsigned long long sum[3];
+};
+__device__ __forceinline__ void label_acc_reset(LabelAcc &a)
+{
+    a.cnt = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.mn[k] = 0xFFFFFFFFu;
+        a.mx[k] = 0u;
+        a.sum[k] = 0ull;
+    }
+}
+__device__ __forceinline__ void label_acc_merge(LabelAcc &a, const LabelAcc &b)
+{
+    a.cnt += b.cnt;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        a.mn[k] = b.mn[k] < a.mn[k] ? b.mn[k] : a.mn[k];
+        a.mx[k] = b.mx[k] > a.mx[k] ? b.mx[k] : a.mx[k];
+        a.sum[k] += b.sum[k];
+    }
+}
+__device__ __forceinline__ unsigned long long shfl_xor_u64(unsigned long long v, int off)
+{
+    const uint32_t lo = __shfl_xor((uint32_t)v, off, 64), hi = __shfl_xor((uint32_t)(v >> 32), off, 64);
+    return ((unsigned long long)hi << 32) | lo;
+}
+// a over the lanes with `member` (the others give the identity); every lane of the wave calls it
+__device__ __forceinline__ LabelAcc label_acc_wave(const LabelAcc &a, bool member)
+{
+    LabelAcc r;
+    label_acc_reset(r);
+    if (member) r = a;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        LabelAcc o;
+        o.cnt = __shfl_xor(r.cnt, off, 64);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            o.mn[k] = __shfl_xor(r.mn[k], off, 64);
+            o.mx[k] = __shfl_xor(r.mx[k], off, 64);
+            o.sum[k] = shfl_xor_u64(r.sum[k], off);
+        }
+        label_acc_merge(r, o);
+    }
+    return r;
+}
+// a into a record: integer atomics, mx already half open (index + 1).  (rec is null for a record
+// index beyond the table, which no label of a flattened array has: nothing is written then.)
+__device__ __forceinline__ void label_acc_flush(LabelRecord *rec, const LabelAcc &a)
+{
+    if (a.cnt == 0u || !rec) return;
+    atomicAdd(&rec->voxels, (unsigned long long)a.cnt);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        atomicMin(&rec->bmin[k], a.mn[k]);
+        atomicMax(&rec->bmax[k], a.mx[k]);
+        atomicAdd(&rec->sum[k], a.sum[k]);
+    }
+}
+// The record index of the component with label lab: the roots below its root, from the root table.
+__device__ __forceinline__ uint32_t label_rank(const LabelArgs &A, uint32_t lab)
+{
+    const uint32_t r = lab - 1u, w = r >> 6;
+    return A.chunk[r / kLabelChunk] + A.wpre[w] + (uint32_t)__popcll(A.mask[w] & ((1ull << (r & 63u)) - 1ull));
+}
+__device__ __forceinline__ LabelRecord *label_record(const LabelArgs &A, uint32_t lab)
+{
+    const uint32_t i = label_rank(A, lab);
+    return i < A.ncomps ? static_cast<LabelRecord *>(A.comps) + i : nullptr;
+}
+// Volume voxel index of box-linear index l.
+__device__ __forceinline__ void label_coords(const LabelArgs &A, uint32_t l, uint32_t c[3])
+{
+    const uint32_t row = l / A.ext[0];
+    c[0] = l - row * A.ext[0] + A.blo[0];
+    const uint32_t zb = row / A.ext[1];
+    c[1] = row - zb * A.ext[1] + A.blo[1];
+    c[2] = zb + A.blo[2];
+}
+
+// Pass 4b.  The records before the sums: the identities of the reductions.
+__global__ __launch_bounds__(256) void label_table_init_kernel(const LabelArgs A)
+{
+    LabelRecord *rec = static_cast<LabelRecord *>(A.comps);
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < (uint64_t)A.ncomps;
+         i += (uint64_t)gridDim.x * 256u) {
+        LabelRecord r;
+        r.label = r.reserved = 0u;
+        r.voxels = 0ull;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            r.bmin[k] = 0xFFFFFFFFu;
+            r.bmax[k] = 0u;
+            r.sum[k] = 0ull;
+        }
+        rec[i] = r;
+    }
+}
+
+// Pass 4c.  Count, bounding box and index sums per component.  A workgroup walks chunks
+// (grid-stride), a lane keeps the sums of its current label in registers for as long as its voxels
+// carry that label -- through a 15-million-voxel component, to the end -- and hands them on when
+// the label changes: at most kLabelWaveRounds times the wave's first pending lane's label is
+// combined over the lanes that share it and handed on by one lane, what is left goes singly.
+// Handing on is an add into the workgroup's LDS slot of that label (kLabelSlots slots, claimed by a
+// compare-and-swap on the slot's key; the label that finds its slot taken by another adds to its
+// record in memory instead), and the slots go to the records once, at the workgroup's end: a large
+// component, which every lane returns to after each speck it crosses, costs a workgroup one set
+// of memory atomics instead of one per return.  Every sum is an integer, so no order shows in the
+// result.  A root also stores its record's label.
+constexpr int kLabelWaveRounds = 2;
+constexpr uint32_t kLabelSlots = 64;
+__global__ __launch_bounds__(256) void label_accum_kernel(const LabelArgs A)
+{
+    __shared__ LabelAcc s_acc[kLabelSlots];
+    __shared__ uint32_t s_key[kLabelSlots];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t *__restrict__ P = A.P;
+    if (tid < kLabelSlots) {
+        s_key[tid] = 0u;
+        label_acc_reset(s_acc[tid]);
+    }
+    __syncthreads();
+    uint32_t key = 0;  // the label the lane gathers for; 0: none
+    LabelAcc acc;
+    label_acc_reset(acc);
+    // r, gathered for label lab, into the label's slot or its record
+    auto add = [&](uint32_t lab, const LabelAcc &r) __attribute__((always_inline)) {
+        const uint32_t slot = (lab * 0x9E3779B1u) >> 26;
+        static_assert(kLabelSlots == 64, "the hash keeps 6 bits");
+        const uint32_t old = atomicCAS(&s_key[slot], 0u, lab);
+        if (old == 0u || old == lab) {
+            LabelAcc &t = s_acc[slot];
+            atomicAdd(&t.cnt, r.cnt);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                atomicMin(&t.mn[k], r.mn[k]);
+                atomicMax(&t.mx[k], r.mx[k]);
+                atomicAdd(&t.sum[k], r.sum[k]);
+            }
+        } else {
+            label_acc_flush(label_record(A, lab), r);
+        }
+    };
+    // the lanes with `pend` hand their sums on; every lane of the wave calls it
+    auto hand_on = [&](bool pend) __attribute__((always_inline)) {
+#pragma unroll
+        for (int round = 0; round < kLabelWaveRounds; ++round) {
+            const unsigned long long todo = __ballot(pend);
+            if (!todo) break;  // wave-uniform
+            const int leader = __ffsll((long long)todo) - 1;
+            const uint32_t lk = (uint32_t)__shfl((int)key, leader, 64);
+            const bool same = pend && key == lk;
+            const LabelAcc r = label_acc_wave(acc, same);
+            if ((int)lane == leader) add(lk, r);
+            if (same) {
+                key = 0;
+                label_acc_reset(acc);
+            }
+            pend = pend && !same;
+        }
+        if (pend) {
+            add(key, acc);
+            key = 0;
+            label_acc_reset(acc);
+        }
+    };
+    for (uint32_t ch = blockIdx.x; ch < A.nchunks; ch += gridDim.x) {
+        const uint64_t base = (uint64_t)ch * kLabelChunk;
+        for (uint32_t it = 0; it < 32u; ++it) {
+            const uint64_t l64 = base + it * 256u + tid;
+            const uint32_t l = (uint32_t)l64;
+            const uint32_t lab = l64 < (uint64_t)A.nvox ? P[(size_t)l] : 0u;
+            const bool change = lab != 0u && key != 0u && lab != key;
+            if (__any(change)) hand_on(change);
+            if (lab != 0u) {
+                if (lab == l + 1u)
+                    if (LabelRecord *own = label_record(A, lab)) own->label = lab;
+                uint32_t c[3];
+                label_coords(A, l, c);
+                key = lab;
+                ++acc.cnt;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    acc.mn[k] = c[k] < acc.mn[k] ? c[k] : acc.mn[k];
+                    acc.mx[k] = c[k] + 1u > acc.mx[k] ? c[k] + 1u : acc.mx[k];
+                    acc.sum[k] += c[k];
+                }
+            }
+        }
+    }
+    hand_on(key != 0u);
+    __syncthreads();
+    if (tid < kLabelSlots && s_key[tid] != 0u) label_acc_flush(label_record(A, s_key[tid]), s_acc[tid]);
+}
+
+// Pass 4d.  The largest component: the maximum of voxels : ~label in 64 bits (most voxels, ties to
+// the smallest label; a component has at most 2^32 - 1 voxels), into out[2].
+__global__ __launch_bounds__(256) void label_largest_kernel(const LabelArgs A)
+{
+    const LabelRecord *rec = static_cast<const LabelRecord *>(A.comps);
+    unsigned long long best = 0ull;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < (uint64_t)A.ncomps;
+         i += (uint64_t)gridDim.x * 256u) {
+        const unsigned long long k = (rec[i].voxels << 32) | (unsigned long long)(~rec[i].label);
+        best = k > best ? k : best;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = shfl_xor_u64(best, off);
+        best = o > best ? o : best;
+    }
+    if ((threadIdx.x & 63u) == 0 && best) atomicMax(&A.out[2], best);
+}
+
+// Region growing: the mask byte of every voxel of N (1 where the label is the seed's), and the
+// seed's component's sums into record 0 -- per lane, per wave, per workgroup through LDS, then one
+// lane's atomics.
+__global__ __launch_bounds__(256) void label_grow_kernel(const LabelArgs A)
+{
+    __shared__ LabelAcc s_acc[4];
+    const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    const uint32_t *__restrict__ P = A.P;
+    uint8_t *__restrict__ out = A.grow;
+    LabelAcc acc;
+    label_acc_reset(acc);
+    for (uint64_t l64 = (uint64_t)blockIdx.x * 256u + tid; l64 < (uint64_t)A.nvox; l64 += (uint64_t)gridDim.x * 256u) {
+        const uint32_t l = (uint32_t)l64;
+        const bool hit = P[(size_t)l] == A.seed_label;
+        out[(size_t)l] = hit ? (uint8_t)1 : (uint8_t)0;
+        if (hit) {
+            uint32_t c[3];
+            label_coords(A, l, c);
+            ++acc.cnt;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                acc.mn[k] = c[k] < acc.mn[k] ? c[k] : acc.mn[k];
+                acc.mx[k] = c[k] + 1u > acc.mx[k] ? c[k] + 1u : acc.mx[k];
+                acc.sum[k] += c[k];
+            }
+        }
+    }
+    const LabelAcc r = label_acc_wave(acc, true);
+    if (lane == 0) s_acc[wave] = r;
+    __syncthreads();
+    if (tid == 0) {
+        LabelAcc t = s_acc[0];
+        for (uint32_t i = 1; i < 4u; ++i) label_acc_merge(t, s_acc[i]);
+        label_acc_flush(static_cast<LabelRecord *>(A.comps), t);
+    }
+}
+
 // One thread per brick: 0 if the brick can produce a visible sample, kSkipCap if EMPTY.
 // Brick b is empty when every density d the trilinear filter can produce from its values maps
 // to TF texels of alpha 0.  d lies in [lo, hi] up to the filter's rounding (3 levels of fmaf
@@ -3972,6 +4546,71 @@ hipError_t launch_mesh_vertices(int layout, bool normals, const MeshArgs &a, hip
 hipError_t launch_mesh_quads(int layout, const MeshArgs &a, hipStream_t stream)
 {
     return launch_mesh_pass(layout, 3, a, stream);
+}
+
+namespace {
+template <typename VT>
+void launch_label_tag(int connectivity, int pass, const LabelArgs &a, uint32_t nlocal, uint32_t nseam,
+                      hipStream_t stream)
+{
+    using G = GeomOf<VT>;
+    if (connectivity == 6) {
+        if (pass == 0) hipLaunchKernelGGL((label_local_kernel<VT, 6>), dim3(nlocal), dim3(256), 0, stream, a);
+        if (pass == 1) hipLaunchKernelGGL((label_seam_kernel<6, G>), dim3(nseam), dim3(256), 0, stream, a);
+    } else {
+        if (pass == 0) hipLaunchKernelGGL((label_local_kernel<VT, 26>), dim3(nlocal), dim3(256), 0, stream, a);
+        if (pass == 1) hipLaunchKernelGGL((label_seam_kernel<26, G>), dim3(nseam), dim3(256), 0, stream, a);
+    }
+}
+}  // namespace
+
+hipError_t launch_label(int layout, int connectivity, int pass, const LabelArgs &a, hipStream_t stream,
+                        std::string *name)
+{
+    const int tag = mesh_tag(layout);
+    if (pass < 0 || pass >= kLabelPasses || tag < 0 || a.nwork == 0 || a.nvox == 0 || (connectivity != 6 && connectivity != 26) ||
+        a.nchunks != (uint32_t)(((uint64_t)a.nvox + kLabelChunk - 1) / kLabelChunk))
+        return hipErrorInvalidValue;
+    if (name)
+        *name = std::string("void vr::(anonymous namespace)::label_local_kernel<") + kTagNames[tag] + ", " +
+                std::to_string(connectivity) + ">(vr::LabelArgs)";
+    const uint32_t nlocal = a.nwork < kLabelMaxGrid ? a.nwork : kLabelMaxGrid;
+    const uint64_t rowgroups = ((uint64_t)a.ext[1] * a.ext[2] + 3) / 4;
+    const uint32_t nseam = rowgroups < kLabelMaxGrid ? (uint32_t)rowgroups : kLabelMaxGrid;
+    if (pass == 2) hipLaunchKernelGGL(label_flatten_kernel, dim3(a.nchunks), dim3(256), 0, stream, a);
+    if (pass == 3) hipLaunchKernelGGL(label_scan_chunks_kernel, dim3(1), dim3(256), 0, stream, a);
+    if (pass >= 2) return hipGetLastError();
+    switch (tag) {
+        case TAG_U8: launch_label_tag<uint8_t>(connectivity, pass, a, nlocal, nseam, stream); break;
+        case TAG_I8: launch_label_tag<int8_t>(connectivity, pass, a, nlocal, nseam, stream); break;
+        case TAG_U16: launch_label_tag<uint16_t>(connectivity, pass, a, nlocal, nseam, stream); break;
+        case TAG_I16: launch_label_tag<int16_t>(connectivity, pass, a, nlocal, nseam, stream); break;
+        case TAG_F32: launch_label_tag<float>(connectivity, pass, a, nlocal, nseam, stream); break;
+        case TAG_QUAD_U8: launch_label_tag<Quad8<uint8_t>>(connectivity, pass, a, nlocal, nseam, stream); break;
+        default: launch_label_tag<Quad8<int8_t>>(connectivity, pass, a, nlocal, nseam, stream); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_label_table(int pass, const LabelArgs &a, hipStream_t stream)
+{
+    if (pass < 0 || pass > 2 || a.ncomps == 0 || !a.comps) return hipErrorInvalidValue;
+    const uint32_t per = (a.ncomps + 255u) / 256u;
+    const uint32_t ninit = per < kLabelMaxGrid ? per : kLabelMaxGrid;
+    const uint32_t nacc = a.nchunks < kLabelMaxGrid ? a.nchunks : kLabelMaxGrid;
+    if (pass == 0) hipLaunchKernelGGL(label_table_init_kernel, dim3(ninit), dim3(256), 0, stream, a);
+    if (pass == 1) hipLaunchKernelGGL(label_accum_kernel, dim3(nacc), dim3(256), 0, stream, a);
+    if (pass == 2) hipLaunchKernelGGL(label_largest_kernel, dim3(ninit), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_label_grow(const LabelArgs &a, hipStream_t stream)
+{
+    if (a.nvox == 0 || !a.grow || !a.comps || a.seed_label == 0) return hipErrorInvalidValue;
+    const uint64_t per = ((uint64_t)a.nvox + 255u) / 256u;
+    const uint32_t n = per < kLabelMaxGrid ? (uint32_t)per : kLabelMaxGrid;
+    hipLaunchKernelGGL(label_grow_kernel, dim3(n), dim3(256), 0, stream, a);
+    return hipGetLastError();
 }
 
 namespace {

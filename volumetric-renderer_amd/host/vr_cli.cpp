@@ -33,6 +33,12 @@
 //                                        PLY in voxel units and print its three counts as one
 //                                        JSON line.  :open leaves the surface open where a face of
 //                                        the volume cuts it)
+//          [--label LO:HI[:26] [--seed X,Y,Z]]   (in place of the image, label the connected
+//                                        components of the value window [LO, HI] -- either may be
+//                                        inf or -inf -- under 6- or (:26) 26-connectivity,
+//                                        include/vr/vr_label.h, and print the info as one JSON
+//                                        line; with a seed, a volume voxel index, also the record
+//                                        of the seed's component as "seed")
 #include <cmath>
 #include <chrono>
 #include <cstdio>
@@ -86,7 +92,8 @@ int main(int argc, char **argv)
                              "[--frames K] [--device-mask M] [--mode composite|mip|iso|minip|mean] [--iso V] "
                              "[--mpr axial|coronal|sagittal:POSITION[:NSAMPLES:SPACING:max|min|mean]] "
                              "[--histogram N[:LO:HI]] [--window P_LO:P_HI] "
-                             "[--pick X,Y --hit entry|opacity|max|min|iso[:THRESHOLD]] [--mesh OUT.ply[:open]]\n",
+                             "[--pick X,Y --hit entry|opacity|max|min|iso[:THRESHOLD]] [--mesh OUT.ply[:open]] "
+                             "[--label LO:HI[:26] [--seed X,Y,Z]]\n",
                      argv[0]);
         return 2;
     }
@@ -95,7 +102,7 @@ int main(int argc, char **argv)
     float radius = 3.0f, rx = 0.0f, ry = 0.0f, ert = 0.0f, iso = 0.0f;
     int shading = 0, skip_empty = 0, frames = 1, exact_gradient = 0;
     uint32_t mask = 0;
-    std::string tfname = "default", mode = "composite", mpr, hist, window, pick, hit, mesh;
+    std::string tfname = "default", mode = "composite", mpr, hist, window, pick, hit, mesh, label, seed;
     for (int i = 3; i < argc; ++i) {
         std::string a = argv[i];
         if (a == "--size" && i + 1 < argc) std::sscanf(argv[++i], "%ux%u", &W, &H);
@@ -114,6 +121,8 @@ int main(int argc, char **argv)
         else if (a == "--pick" && i + 1 < argc) pick = argv[++i];
         else if (a == "--hit" && i + 1 < argc) hit = argv[++i];
         else if (a == "--mesh" && i + 1 < argc) mesh = argv[++i];
+        else if (a == "--label" && i + 1 < argc) label = argv[++i];
+        else if (a == "--seed" && i + 1 < argc) seed = argv[++i];
         else if (a == "--frames" && i + 1 < argc) frames = std::atoi(argv[++i]);
         else if (a == "--device-mask" && i + 1 < argc) mask = (uint32_t)std::strtoul(argv[++i], nullptr, 0);
         else {
@@ -198,6 +207,26 @@ int main(int argc, char **argv)
         }
         hit_threshold = (float)th;
     }
+    // --label LO:HI[:26] [--seed X,Y,Z]
+    float label_lo = 0.0f, label_hi = 0.0f;
+    uint32_t label_conn = 6, seed_xyz[3] = {0, 0, 0};
+    if (!label.empty() || !seed.empty()) {
+        const std::vector<std::string> f = split_colons(label);
+        double lo = 0.0, hi = 0.0;
+        char tail = 0;
+        bool ok = (f.size() == 2 || (f.size() == 3 && f[2] == "26")) && parse_double(f[0], &lo) &&
+                  parse_double(f[1], &hi) && lo <= hi;
+        if (ok && !seed.empty())
+            ok = std::sscanf(seed.c_str(), "%u,%u,%u%c", &seed_xyz[0], &seed_xyz[1], &seed_xyz[2], &tail) == 3;
+        if (!ok) {
+            std::fprintf(stderr, "bad --label %s --seed %s (LO:HI[:26] with LO <= HI, and X,Y,Z)\n", label.c_str(),
+                         seed.c_str());
+            return 2;
+        }
+        label_lo = (float)lo;
+        label_hi = (float)hi;
+        label_conn = f.size() == 3 ? 26u : 6u;
+    }
     try {
         Vol::Rendering::Hip::OffscreenPass pass = mask ? Vol::Rendering::Hip::OffscreenPass(
                                                              nullptr, W, H, Vol::Rendering::Hip::DeviceMask{mask})
@@ -263,6 +292,38 @@ int main(int argc, char **argv)
             std::printf("{\"vertices\": %llu, \"triangles\": %llu, \"inside_voxels\": %llu}\n",
                         (unsigned long long)m.info.vertices, (unsigned long long)m.info.triangles,
                         (unsigned long long)m.info.inside_voxels);
+            return 0;
+        }
+        if (!label.empty()) {  // the components of a value window in place of the image
+            // one labelling: the seed's record is the one its label names
+            const auto l = pass.label_components(label_lo, label_hi, label_conn);
+            const vr_label_info &info = l.info;
+            vr_label_component c{};
+            if (!seed.empty()) {
+                uint32_t dims[3] = {0, 0, 0};
+                vr_debug_volume_info(pass.handle(), dims, nullptr, nullptr);
+                if (seed_xyz[0] >= dims[0] || seed_xyz[1] >= dims[1] || seed_xyz[2] >= dims[2])
+                    throw std::runtime_error("seed lies outside the volume");
+                const uint32_t lab = l.labels[seed_xyz[0] + (size_t)dims[0] * (seed_xyz[1] + (size_t)dims[1] * seed_xyz[2])];
+                size_t a = 0, b = l.components.size();  // sorted by label
+                while (a < b) {
+                    const size_t m = (a + b) / 2;
+                    if (l.components[m].label < lab) a = m + 1; else b = m;
+                }
+                if (lab && a < l.components.size() && l.components[a].label == lab) c = l.components[a];
+            }
+            std::printf("{\"voxels\": %llu, \"in_voxels\": %llu, \"components\": %llu, \"largest_voxels\": %llu, "
+                        "\"largest_label\": %u",
+                        (unsigned long long)info.voxels, (unsigned long long)info.in_voxels,
+                        (unsigned long long)info.components, (unsigned long long)info.largest_voxels,
+                        info.largest_label);
+            if (!seed.empty())
+                std::printf(", \"seed\": {\"label\": %u, \"voxels\": %llu, \"bbox_min\": [%u, %u, %u], "
+                            "\"bbox_max\": [%u, %u, %u], \"sum\": [%llu, %llu, %llu]}",
+                            c.label, (unsigned long long)c.voxels, c.bbox_min[0], c.bbox_min[1], c.bbox_min[2],
+                            c.bbox_max[0], c.bbox_max[1], c.bbox_max[2], (unsigned long long)c.sum[0],
+                            (unsigned long long)c.sum[1], (unsigned long long)c.sum[2]);
+            std::printf("}\n");
             return 0;
         }
         if (!window.empty()) {  // the percentile window of a 4096-bin histogram over the exact range

@@ -131,6 +131,21 @@ class vr_mesh_info(C.Structure):  # vr_mesh.h
                 ("reserved", C.c_uint64)]
 
 
+class vr_label_request(C.Structure):  # vr_label.h
+    _fields_ = [("lo", C.c_float), ("hi", C.c_float), ("connectivity", C.c_uint32),
+                ("use_box", C.c_uint32), ("box_min", C.c_uint32 * 3), ("box_max", C.c_uint32 * 3)]
+
+
+class vr_label_component(C.Structure):  # vr_label.h
+    _fields_ = [("label", C.c_uint32), ("reserved", C.c_uint32), ("voxels", C.c_uint64),
+                ("bbox_min", C.c_uint32 * 3), ("bbox_max", C.c_uint32 * 3), ("sum", C.c_uint64 * 3)]
+
+
+class vr_label_info(C.Structure):  # vr_label.h
+    _fields_ = [("voxels", C.c_uint64), ("in_voxels", C.c_uint64), ("components", C.c_uint64),
+                ("largest_voxels", C.c_uint64), ("largest_label", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -168,7 +183,7 @@ DIST_ID_BYTES = 128  # include/vr/vr_dist.h VR_DIST_ID_BYTES
 DEBUG_SYMBOLS = ["vr_debug_set_knob", "vr_debug_get_knob", "vr_debug_timing_member",
                  "vr_debug_create_members", "vr_debug_fail_member",
                  "vr_debug_host_profile_enable", "vr_debug_host_profile_member",
-                 "vr_debug_variant_name", "vr_debug_last_kernel_name",
+                 "vr_debug_variant_name", "vr_debug_last_kernel_name", "vr_debug_label_pass_ms",
                  "vr_debug_ymajor_copy_bytes", "vr_debug_ymajor_field_bytes"]
 # include/vr/vr_modes.h: render modes (context state) and enum vr_render_mode
 MODES_SYMBOLS = ["vr_set_render_mode", "vr_get_render_mode"]
@@ -194,6 +209,11 @@ HIT_MISS_STEP = 0xFFFFFFFF
 MESH_SYMBOLS = ["vr_mesh_count", "vr_mesh_extract", "vr_mesh_extract_device"]
 MESH_VERTEX_DTYPE = np.dtype([("pos", "<f4", 3), ("normal", "<f4", 3)])
 ENOSPC = -28  # VR_ENOSPC
+# include/vr/vr_label.h: connected components of a value window and seeded region growing
+LABEL_SYMBOLS = ["vr_label_count", "vr_label_components", "vr_label_components_device",
+                 "vr_region_grow", "vr_region_grow_device"]
+LABEL_COMPONENT_DTYPE = np.dtype([("label", "<u4"), ("reserved", "<u4"), ("voxels", "<u8"),
+                                  ("bbox_min", "<u4", 3), ("bbox_max", "<u4", 3), ("sum", "<u8", 3)])
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -307,6 +327,15 @@ def lib() -> C.CDLL:
                           u32, u32, C.POINTER(vr_hit)]),
         "vr_mesh_write_ply": (i32, [C.c_char_p, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(f32),
                                     C.POINTER(f32)]),
+        "vr_label_count": (i32, [vp, C.POINTER(vr_label_request), C.POINTER(vr_label_info)]),
+        "vr_label_components": (i32, [vp, C.POINTER(vr_label_request), vp, C.c_uint64, vp, C.c_uint64,
+                                      C.POINTER(vr_label_info)]),
+        "vr_label_components_device": (i32, [vp, C.POINTER(vr_label_request), vp, C.c_uint64, vp,
+                                             C.c_uint64, C.POINTER(vr_label_info), vp]),
+        "vr_region_grow": (i32, [vp, C.POINTER(vr_label_request), C.POINTER(C.c_uint32), vp, C.c_uint64,
+                                 C.POINTER(vr_label_component)]),
+        "vr_region_grow_device": (i32, [vp, C.POINTER(vr_label_request), C.POINTER(C.c_uint32), vp,
+                                        C.c_uint64, C.POINTER(vr_label_component), vp]),
         "vr_mesh_count": (i32, [vp, C.POINTER(vr_mesh_request), C.POINTER(vr_mesh_info)]),
         "vr_mesh_extract": (i32, [vp, C.POINTER(vr_mesh_request), vp, C.c_uint64, vp, C.c_uint64,
                                   C.POINTER(vr_mesh_info)]),
@@ -316,6 +345,7 @@ def lib() -> C.CDLL:
         "vr_debug_fail_member": (i32, [vp, i32, C.c_uint64]),
         "vr_debug_variant_name": (i32, [C.POINTER(vr_variant_facts), C.c_char_p, C.c_size_t]),
         "vr_debug_last_kernel_name": (C.c_char_p, [vp]),
+        "vr_debug_label_pass_ms": (i32, [vp, C.POINTER(C.c_float)]),
         "vr_debug_ymajor_copy_bytes": (C.c_uint64, [vp]),
         "vr_debug_ymajor_field_bytes": (C.c_uint64, [vp]),
         "vr_cam_init": (None, [C.POINTER(vr_orbit_camera)]),
@@ -397,6 +427,24 @@ def mesh_request(iso: float, closed=True, normals=True, box=None) -> vr_mesh_req
         for a in range(3):
             req.box_min[a], req.box_max[a] = int(box[0][a]), int(box[1][a])
     return req
+
+
+def label_request(lo: float, hi: float, connectivity=6, box=None) -> vr_label_request:
+    """A vr_label_request: the window [lo, hi] (density units, either may be infinite), the
+    connectivity (6 or 26) and the voxel box ((x0, y0, z0), (x1, y1, z1)), half open, or None for
+    the whole volume."""
+    req = vr_label_request()
+    req.lo, req.hi, req.connectivity = float(lo), float(hi), int(connectivity)
+    if box is not None:
+        req.use_box = 1
+        for a in range(3):
+            req.box_min[a], req.box_max[a] = int(box[0][a]), int(box[1][a])
+    return req
+
+
+def label_component_dict(comp: vr_label_component) -> dict:
+    return {"label": comp.label, "voxels": comp.voxels, "bbox_min": tuple(comp.bbox_min),
+            "bbox_max": tuple(comp.bbox_max), "sum": tuple(comp.sum)}
 
 
 def write_ply(path: str, verts, tris, scale=None, offset=None) -> None:
@@ -873,6 +921,92 @@ class OffscreenPass:
                                                  C.c_void_p(tris_ptr), int(tcap), C.byref(info),
                                                  C.c_void_p(stream or None)), "mesh_device")
         return self._mesh_info(info)
+
+    # -- connected components and region growing (vr_label.h) --
+    LABEL_PASSES = ("local", "seam", "flatten", "scan", "table_init", "accumulate", "largest", "grow")
+
+    def label_pass_ms(self) -> dict:
+        """vr_debug_label_pass_ms: kernel ms of each pass of the last label or region-grow call
+        (timing enabled), by name."""
+        ms = (C.c_float * 8)()
+        self._check(lib().vr_debug_label_pass_ms(self._ctx, ms), "label_pass_ms")
+        return dict(zip(self.LABEL_PASSES, (float(v) for v in ms)))
+
+    @staticmethod
+    def _label_info(info: vr_label_info) -> dict:
+        return {"voxels": info.voxels, "in_voxels": info.in_voxels, "components": info.components,
+                "largest_voxels": info.largest_voxels, "largest_label": info.largest_label}
+
+    def _label_shape(self, box):
+        """(bz, by, bx) of the box, or of the volume.  (A box the library will refuse -- empty or
+        inverted -- gives empty axes here: the call is still made, and raises.)"""
+        if box is not None:
+            return tuple(max(int(box[1][a]) - int(box[0][a]), 0) for a in (2, 1, 0))
+        d = self.volume_info()[0]
+        return (int(d[2]), int(d[1]), int(d[0]))
+
+    def label_count(self, lo: float, hi: float, connectivity=6, box=None) -> dict:
+        """vr_label_count: the voxels, in voxels, components and largest component of the window."""
+        req = label_request(lo, hi, connectivity, box)
+        info = vr_label_info()
+        self._check(lib().vr_label_count(self._ctx, C.byref(req), C.byref(info)), "label_count")
+        return self._label_info(info)
+
+    def label(self, lo: float, hi: float, connectivity=6, box=None):
+        """vr_label_components: (labels (bz, by, bx) uint32, records as LABEL_COMPONENT_DTYPE sorted
+        by label, info dict).  One labelling where the table has at most 65536 records; a larger
+        one is sized by the first call's VR_ENOSPC info and labelled once more."""
+        req = label_request(lo, hi, connectivity, box)
+        info = vr_label_info()
+        shape = self._label_shape(box)
+        n = shape[0] * shape[1] * shape[2]
+        labels = np.zeros(max(n, 1), np.uint32)  # (never a NULL buffer)
+        cap = 1 << 16
+        comps = np.zeros(cap, LABEL_COMPONENT_DTYPE)
+        rc = lib().vr_label_components(self._ctx, C.byref(req), labels.ctypes.data, n,
+                                       comps.ctypes.data, cap, C.byref(info))
+        if rc == ENOSPC and int(info.voxels) == n and int(info.components) > cap:
+            cap = int(info.components)
+            comps = np.zeros(cap, LABEL_COMPONENT_DTYPE)
+            rc = lib().vr_label_components(self._ctx, C.byref(req), labels.ctypes.data, n,
+                                           comps.ctypes.data, cap, C.byref(info))
+        self._check(rc, "label")
+        return labels[:n].reshape(shape), comps[:int(info.components)], self._label_info(info)
+
+    def label_device(self, labels_ptr: int, lcap: int, comps_ptr: int, ccap: int, lo: float, hi: float,
+                     connectivity=6, box=None, stream: int = 0) -> dict:
+        """vr_label_components_device: lcap labels and ccap records into device memory on `stream`;
+        returns the info dict when both buffers are complete."""
+        req = label_request(lo, hi, connectivity, box)
+        info = vr_label_info()
+        self._check(lib().vr_label_components_device(self._ctx, C.byref(req), C.c_void_p(labels_ptr), int(lcap),
+                                                     C.c_void_p(comps_ptr), int(ccap), C.byref(info),
+                                                     C.c_void_p(stream or None)), "label_device")
+        return self._label_info(info)
+
+    def region_grow(self, seed, lo: float, hi: float, connectivity=6, box=None):
+        """vr_region_grow: (mask (bz, by, bx) uint8 of the seed's component, its record as a dict).
+        seed: the (x, y, z) volume voxel index."""
+        req = label_request(lo, hi, connectivity, box)
+        shape = self._label_shape(box)
+        n = shape[0] * shape[1] * shape[2]
+        mask = np.zeros(max(n, 1), np.uint8)  # (never a NULL buffer)
+        comp = vr_label_component()
+        sd = (C.c_uint32 * 3)(*[int(v) & 0xFFFFFFFF for v in seed])
+        self._check(lib().vr_region_grow(self._ctx, C.byref(req), sd, mask.ctypes.data, n,
+                                         C.byref(comp)), "region_grow")
+        return mask[:n].reshape(shape), label_component_dict(comp)
+
+    def region_grow_device(self, seed, mask_ptr: int, mcap: int, lo: float, hi: float, connectivity=6,
+                           box=None, stream: int = 0) -> dict:
+        """vr_region_grow_device: the mask into device memory (mcap bytes) on `stream`; returns the
+        component's record when the mask is complete."""
+        req = label_request(lo, hi, connectivity, box)
+        comp = vr_label_component()
+        sd = (C.c_uint32 * 3)(*[int(v) for v in seed])
+        self._check(lib().vr_region_grow_device(self._ctx, C.byref(req), sd, C.c_void_p(mask_ptr), int(mcap),
+                                                C.byref(comp), C.c_void_p(stream or None)), "region_grow_device")
+        return label_component_dict(comp)
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
