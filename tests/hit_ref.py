@@ -53,9 +53,11 @@ class Walk:
         return self.records[key]["step"] != MISS_STEP
 
 
-def walk(scene, iso=0.0, thresholds=(0.5,)):
+def walk(scene, iso=0.0, thresholds=(0.5,), rect=None):
     """scene: pyoracle.Scene (its step, ray_dist, slice box, window and TF are used; shading and
-    ert_eps are not)."""
+    ert_eps are not).  rect = (x0, y0, w, h): walk the pixels of that rectangle only; the arrays
+    keep the frame's shape, every other pixel stays a miss and uncovered, and the counters are
+    those of the rectangle."""
     s = scene.s
     W, H = s.width, s.height
     vol = np.ascontiguousarray(scene.vol, dtype=np.float32)
@@ -75,6 +77,8 @@ def walk(scene, iso=0.0, thresholds=(0.5,)):
         nsteps = int(F(s.ray_dist) / step)
     one, zero, half = F(1.0), F(0.0), F(0.5)
     out = Walk(H, W, keys)
+    x0, y0, rw, rh = (0, 0, W, H) if rect is None else (int(v) for v in rect)
+    assert 0 <= x0 and 0 <= y0 and rw >= 1 and rh >= 1 and x0 + rw <= W and y0 + rh <= H
 
     def tri(p):
         return F(L.or_trilinear(vp, nx, ny, nz, C.c_float(p[0]), C.c_float(p[1]), C.c_float(p[2])))
@@ -98,8 +102,8 @@ def walk(scene, iso=0.0, thresholds=(0.5,)):
         r["step"][py, px] = k
 
     with np.errstate(all="ignore"):
-        for py in range(H):
-            for px in range(W):
+        for py in range(y0, y0 + rh):
+            for px in range(x0, x0 + rw):
                 ok, tex, _frag, d = scene.pixel_ray(px, py)
                 if not ok:
                     continue
