@@ -139,6 +139,9 @@ def test_dist_entry_points_reject_bad_arguments():
 def test_no_cpu_fallback_in_product():
     """The product path never routes through the oracle or any CPU renderer."""
     for path in ("volumetric-renderer_amd/vr_amd.py", "volumetric-renderer_amd/csrc/vr_api.hip",
+                 "volumetric-renderer_amd/csrc/vr_api_mpr.hip", "volumetric-renderer_amd/csrc/vr_api_hist.hip",
+                 "volumetric-renderer_amd/csrc/vr_api_hit.hip", "volumetric-renderer_amd/csrc/vr_api_label.hip",
+                 "volumetric-renderer_amd/csrc/vr_api_mesh.hip", "volumetric-renderer_amd/csrc/vr_ctx.h",
                  "volumetric-renderer_amd/csrc/vr_kernels.hip", "volumetric-renderer_amd/host/vr_host.cpp",
                  "volumetric-renderer_amd/csrc/vr_dist.cpp"):
         txt = open(os.path.join(ROOT, path)).read()

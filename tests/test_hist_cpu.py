@@ -232,10 +232,27 @@ def test_host_helpers_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
     assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
     assert "hist harness ok" in r.stdout and "FAILED" not in r.stdout
-    seen = 0
+    seen = boxes = 0
     for line in r.stdout.splitlines():
         w = line.replace(":", " ").split()
-        if w[0] == "edges":
+        if w[0] == "box":
+            # the request-check table: the box rule and the brick range, restated here (no size bound:
+            # the voxel count and the brick count saturate at 2^64 - 1)
+            use = int(w[1])
+            lo, hi, dims = ([int(x) for x in w[a:a + 3]] for a in (2, 5, 9))
+            ok, voxels, nwork = int(w[12]), int(w[13]), int(w[14])
+            if not use:
+                lo, hi = [0, 0, 0], dims
+            assert ok == int(use <= 1 and all(lo[a] < hi[a] <= dims[a] for a in range(3))), line
+            if ok:
+                assert voxels == min((hi[0] - lo[0]) * (hi[1] - lo[1]) * (hi[2] - lo[2]), 2 ** 64 - 1), line
+                cells = (7, 8, 8)
+                nb = [(hi[a] + 1) // cells[a] - (lo[a] + 2) // cells[a] + 1 for a in range(3)]
+                assert nwork == min(nb[0] * nb[1] * nb[2], 2 ** 64 - 1), line
+            else:
+                assert voxels == 0 and nwork == 0, line
+            boxes += 1
+        elif w[0] == "edges":
             lo, hi, n = float.fromhex(w[1]), float.fromhex(w[2]), int(w[3])
             e = hist_ref.edges(lo, hi, n).view(np.uint32)
             step = n // 8 or 1
@@ -249,4 +266,4 @@ def test_host_helpers_under_sanitizers(tmp_path):
             ref = hist_ref.window(b, lo, hi, p0, p1)
             assert int(w[6]) == 1 and [int(w[7], 16), int(w[8], 16)] == [int(x) for x in bits(ref)]
             seen += 1
-    assert seen == 9
+    assert seen == 9 and boxes == 18

@@ -1,7 +1,9 @@
 // hist_harness.cpp — the host side of include/vr/vr_hist.h (csrc/vr_hist_host.h: edges, the bin
-// of a value, the percentile window) as a stand-alone program, built with -fsanitize=address,
-// undefined by tests/test_hist_cpu.py.  It checks the closed forms itself (exit status 1 on a
-// mismatch) and prints the edges' and windows' bits, which the test compares with tests/hist_ref.py.
+// of a value, the percentile window; csrc/vr_box_host.h: the request box and its bricks) as a
+// stand-alone program, built with -fsanitize=address,undefined by tests/test_hist_cpu.py.  It checks
+// the closed forms itself (exit status 1 on a mismatch) and prints the edges' and windows' bits,
+// which the test compares with tests/hist_ref.py, and the resolved boxes, which the test compares
+// with its own statement of the rule.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -84,8 +86,76 @@ static void print_window(const std::vector<uint64_t> &bins, float lo, float hi, 
                 bits(a), bits(b));
 }
 
+// a request's box on a dims volume: what the shared rule (vr_box_host.h, which vr_histogram uses as
+// it is) says, printed for the test in the label harness's format
+static void box_case(uint32_t use_box, const uint32_t lo[3], const uint32_t hi[3], const uint32_t dims[3])
+{
+    // the arrays sit at the very end of heap blocks: a read past [2] is an ASan report
+    std::vector<uint32_t> mn(lo, lo + 3), mx(hi, hi + 3), dm(dims, dims + 3);
+    VoxelBox b;
+    std::memset(&b, 0x77, sizeof b);
+    const VoxelBox before = b;
+    const BoxError e = box_resolve(use_box, mn.data(), mx.data(), dm.data(), &b);
+    bool want = use_box <= 1;
+    unsigned __int128 vox = 1;
+    for (int a = 0; a < 3 && want; ++a) {
+        const uint32_t l = use_box ? lo[a] : 0u, h = use_box ? hi[a] : dims[a];
+        want = l < h && h <= dims[a];
+        if (want) vox *= h - l;
+    }
+    CHECK((e == kBoxOk) == want && (e == kBoxUse) == (use_box > 1));
+    if (e) CHECK(std::memcmp(&b, &before, sizeof b) == 0);  // untouched
+    unsigned long long nwork = 0;
+    if (!e) {
+        for (int a = 0; a < 3; ++a) {
+            CHECK(b.lo[a] == (use_box ? lo[a] : 0u) && b.hi[a] == (use_box ? hi[a] : dims[a]));
+            CHECK(b.ext[a] == b.hi[a] - b.lo[a]);
+        }
+        CHECK(vox >> 64 ? b.voxels == ~0ull : b.voxels == (unsigned long long)vox);  // saturates
+        const uint32_t cells[3] = {7, 8, 8};
+        uint32_t b0[3] = {0, 0, 0}, nb[3] = {0, 0, 0};
+        nwork = box_brick_range(b, cells, 2, b0, nb);
+        for (int a = 0; a < 3; ++a) {
+            // every padded voxel index of the box lies in the bricks b0 .. b0 + nb - 1
+            const unsigned long long first = (unsigned long long)b.lo[a] + 2, last = (unsigned long long)b.hi[a] + 1;
+            CHECK(first / cells[a] == b0[a] && last / cells[a] == (unsigned long long)b0[a] + nb[a] - 1);
+        }
+        const unsigned __int128 prod = (unsigned __int128)nb[0] * nb[1] * nb[2];
+        CHECK(nwork >= 1 && (prod >> 64 ? nwork == ~0ull : nwork == (unsigned long long)prod));
+    }
+    std::printf("box %u  %u %u %u  %u %u %u on %u %u %u: %d  %llu  %llu\n", use_box, lo[0], lo[1], lo[2], hi[0], hi[1],
+                hi[2], dims[0], dims[1], dims[2], (int)(e == kBoxOk), e ? 0ull : (unsigned long long)b.voxels, nwork);
+}
+
 int main()
 {
+    {  // the request box: the label harness's cases but those of its 2^32 - 1 bound
+        const uint32_t M = 0xFFFFFFFFu;
+        const uint32_t dims[3] = {19, 17, 21}, big[3] = {M, M, M}, zero3[3] = {0, 0, 0};
+        struct {
+            uint32_t use, lo[3], hi[3];
+        } cases[] = {
+            {0, {0, 0, 0}, {0, 0, 0}},      // the whole volume: the box is not read for sense
+            {0, {9, 9, 9}, {1, 1, 1}},
+            {1, {0, 0, 0}, {19, 17, 21}},
+            {1, {3, 2, 5}, {15, 13, 18}},
+            {1, {3, 2, 5}, {4, 13, 18}},    // one voxel along x
+            {1, {18, 16, 20}, {19, 17, 21}},
+            {1, {0, 0, 0}, {20, 17, 21}},   // beyond, by one
+            {1, {0, 0, 0}, {19, 18, 21}},
+            {1, {0, 0, 0}, {19, 17, 22}},
+            {1, {3, 3, 3}, {3, 4, 4}},      // empty
+            {1, {3, 5, 3}, {4, 4, 4}},      // min above max
+            {1, {0, 0, M}, {1, 1, 1}},
+            {1, {0, 0, 0}, {1, M, 1}},
+            {2, {0, 0, 0}, {1, 1, 1}},      // use_box
+            {M, {0, 0, 0}, {1, 1, 1}},
+        };
+        for (const auto &c : cases) box_case(c.use, c.lo, c.hi, dims);
+        box_case(0, zero3, zero3, zero3);  // no volume
+        box_case(0, zero3, zero3, big);    // no bound here: the voxel product passes 64 bits and saturates
+        box_case(1, zero3, big, big);
+    }
     edge_values(-1.3f, 2.7f, 1000);
     edge_values(0.0f, 65535.0f, 4096);
     edge_values(-3.0e38f, 3.0e38f, 4096);  // hi - lo overflows f32: the guess is formed in double

@@ -57,7 +57,7 @@ static void box_case(uint32_t use_box, const uint32_t lo[3], const uint32_t hi[3
         CHECK(b.voxels == (unsigned long long)vox && b.voxels <= kLabelMaxVoxels);
         const uint32_t cells[3] = {7, 8, 8};
         uint32_t b0[3] = {0, 0, 0}, nb[3] = {0, 0, 0};
-        nwork = label_brick_range(b, cells, 2, b0, nb);
+        nwork = box_brick_range(b, cells, 2, b0, nb);  // (vr_box_host.h: the shared rule)
         for (int a = 0; a < 3; ++a) {
             // every padded voxel index of the box lies in the bricks b0 .. b0 + nb - 1
             const unsigned long long first = (unsigned long long)b.lo[a] + 2, last = (unsigned long long)b.hi[a] + 1;

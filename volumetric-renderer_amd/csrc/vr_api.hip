@@ -6,202 +6,18 @@
 // the kernel), slicing (:271-277), and update_uniform_buffer (:1152-1171, here: the per-frame
 // unprojection matrix the kernel's ray setup uses).  No exceptions cross the ABI; HIP errors
 // become negative status codes with a message in vr_last_error().
-#include "../../include/vr/vr.h"
-#include "../../include/vr/vr_debug.h"
-#include "../../include/vr/vr_modes.h"
-#include "../../include/vr/vr_iso.h"
-#include "../../include/vr/vr_mpr.h"
-#include "../../include/vr/vr_hist.h"
-#include "../../include/vr/vr_hit.h"
-#include "../../include/vr/vr_label.h"
-#include "../../include/vr/vr_mesh.h"
-#include "vr_internal.h"
-#include "vr_group.h"
+#include "vr_ctx.h"
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
-#include <string>
-#include <vector>
-
-#pragma clang fp contract(off)
-
-using namespace vr;
-
-// vr_render (host output): row bands per frame, each copied to the host while later bands
-// render (kHostBandMinRows rows at least, vr_internal.h).  C3 into pageable host memory, ms
-// per frame, three rounds (profiles/r03/host_bands/): 4 bands 0.589-0.603 shaded, 0.470-0.488
-// unshaded; 8 bands 0.730-0.753 / 0.557-0.560; 16 bands 1.13-1.63 / 0.86-0.90.  A page-locked
-// destination changes nothing (4 bands 0.582 against 0.583; 2 bands 0.635-0.655, both
-// kinds; profiles/r03/host_pinned/): the bands' own launches, not the copies, set the time.
-#ifndef VR_HOST_BANDS
-#define VR_HOST_BANDS 4
-#endif
-constexpr int kRenderBands = VR_HOST_BANDS;
-
-struct vr_ctx {
-    int device = 0;
-    uint32_t width = 0, height = 0;
-    // volume (bricked, native storage type)
-    void *bricks = nullptr;
-    size_t brick_bytes = 0;
-    int storage = ST_F32;
-    int layout = ST_F32;  // brick layout code (storage | kQuadFlag for 8-bit yz-quads)
-    // the last frame's view (view_dense_rows): image x along the bricks' rows, dense sampling
-    bool dense_rows = false;
-    double pixel_span = 0.0;  // voxels per pixel step at the volume centre (view_dense_rows)
-    double axis_align = 1.0;  // largest |component| of the centre ray's unit direction
-    int ray_axis = 2;         // the volume axis of that component (0 x, 1 y, 2 z)
-    double row_align = 1.0;   // |x component| of the unit pixel step along the image x axis
-    // f32 volumes: further resident copies in the alternative geometries (kAltFlag for
-    // oblique views, the plain and stencil copies for sparse ones, the y-major copy for
-    // dense-row views along y), each built lazily on the first frame that wants it after a
-    // volume change
-    struct AltCopy {
-        void *bricks = nullptr;  // stream-ordered allocation (hipMallocAsync)
-        size_t bytes = 0;
-        bool valid = false, failed = false;
-        uint64_t used = 0;  // frame_no of the latest frame that read it (eviction order)
-    } alt[4];
-    uint32_t nx = 1, ny = 1, nz = 1;
-    float vmin = 0.0f, vmax = 1.0f;
-    // transfer function (decoded, linear float RGBA)
-    float4 *tf = nullptr;
-    uint32_t tf_n = 0;
-    uint32_t *tf_nz = nullptr;  // prefix count of nonzero-alpha texels (tf_n + 1)
-    float smin[3] = {0.0f, 0.0f, 0.0f};
-    float smax[3] = {1.0f, 1.0f, 1.0f};
-    int render_mode = VR_MODE_COMPOSITE;  // vr_modes.h: context state, like the slice box
-    float isovalue = 0.0f;                // vr_iso.h: context state, read in VR_MODE_ISO only
-    // empty-space classification (skip_empty), built lazily: per-brick value range after a
-    // volume change, the brick distance field after a volume or TF change
-    float2 *brick_range = nullptr;
-    uint8_t *skip_dist = nullptr;  // 2 x nbricks: distance field + pass scratch
-    size_t nbricks_alloc = 0;
-    bool range_valid = false, dist_valid = false;
-    // f32 shading: precomputed central differences (3 x the bricked density), built lazily
-    // on the first shaded frame after a volume change; absent when memory is short
-    float *grad = nullptr;  // stream-ordered allocation (hipMallocAsync)
-    size_t grad_bytes = 0;
-    bool grad_valid = false;
-    uint64_t grad_used = 0;  // frame_no of the latest frame that read it
-    bool grad_half = false;      // the field's precision (vr_params.exact_gradient == 0: binary16)
-    // the y-major binary16 field (vr_internal.h F32Y; launch_grad_field ymajor): what a shaded
-    // frame on the y-major copy reads in place of `grad`; opportunistic as that copy (ensure_yfield)
-    float *ygrad = nullptr;  // stream-ordered allocation (hipMallocAsync)
-    size_t ygrad_bytes = 0;
-    bool ygrad_valid = false;
-    int ygrad_scale_log2 = 0;
-    int grad_scale_log2 = 0;     // and its scale (field_scale_log2 of the data's own range)
-    // f32 storage: the stored voxels' min and max, zero border included (measured on the bricks
-    // at upload): the binary16 field's scale comes from these, never from the caller's
-    // vmin/vmax, which may be a display window narrower than the data
-    float data_lo = 0.0f, data_hi = 1.0f;
-    // adaptive tile order (tile_order 4): per launch geometry, the last launch's per-tile
-    // durations and the workgroup -> tile permutation built from them
-    // Keyed by the launch stream too: frames in flight on different streams each own their
-    // duration/permutation buffers, so one stream's order kernel never rewrites a permutation
-    // another stream's march kernel is reading.
-    // Keyed by the row shard as well: one stream may render several shares of a frame (the
-    // row bands of vr_render), each with its own tile durations.
-    struct TileSched {
-        uint32_t tiles_x = 0, tiles_y = 0, supers_x = 0, per_xcd = 0;
-        uint32_t row_block = 0, rank = 0, nranks = 0, share_w0 = 1, share_w = 1;
-        int pair = 0;
-        uint32_t kernel = 0;  // variant_tile_key: another kernel's tile durations differ
-        void *stream = nullptr;
-        uint32_t *cost = nullptr, *perm = nullptr, *lists = nullptr;
-        bool have_perm = false;
-        uint32_t launches = 0;
-    };
-    std::vector<TileSched> sched;
-    // lazily built derived fields (gradient, skip-empty) are produced on the stream of the
-    // frame that first needs them; frames on other streams wait for this event
-    hipEvent_t built_ev = nullptr;
-    bool built_recorded = false;
-    // Frame fences (round 6): for each stream that launched frames of this context, an event
-    // recorded after its latest frame.  A derived structure that frames in flight may still read
-    // is freed (or rewritten) stream-ordered on the evicting frame's stream after that stream
-    // waited on every other stream's fence -- no device synchronisation on the frame path.
-    struct Fence {
-        hipStream_t stream;
-        hipEvent_t ev;
-        uint64_t used;
-        bool external;        // recorded by the caller (vr_dist slot streams, vr_group.h)
-        uint64_t build_seen;  // build_gen this stream last waited for (ensure_derived)
-    };
-    std::vector<Fence> fences;
-    uint64_t build_gen = 0;  // records of built_ev so far
-    uint64_t frame_no = 0;  // launches so far (the derived structures' recency)
-    FrameVariant last_variant;  // the last frame or count launch (vr_debug_last_kernel_name)
-    std::string last_mpr_name;  // not empty: an MPR or histogram launch (vr_mpr.h, vr_hist.h) came after it
-    // derived-structure history (vr_memory_report, ABI 9)
-    uint64_t n_builds = 0, n_evictions = 0, n_downgrades = 0;
-    uint32_t last_downgrade = 0;
-    // scratch
-    unsigned long long *counters = nullptr;
-    void *frame_dev = nullptr;
-    size_t frame_bytes = 0;
-    // vr_mpr_render (host output): its image, whose size is the plane's and not the framebuffer's
-    void *mpr_dev = nullptr;
-    size_t mpr_bytes = 0;
-    // vr_histogram (vr_hist.h): HistArgs::out (kHistOutWords 64-bit words), then the edge table
-    void *hist_dev = nullptr;
-    // vr_hit_render, vr_pick (vr_hit.h, host output): the records, grown on demand
-    void *hit_dev = nullptr;
-    size_t hit_bytes = 0;
-    // vr_mesh_* (vr_mesh.h): the passes' scratch (vr_internal.h MeshScratch), and vr_mesh_extract's
-    // device copies of the two host buffers; all grown on demand
-    void *mesh_dev = nullptr, *mesh_out_dev = nullptr;
-    size_t mesh_bytes = 0, mesh_out_bytes = 0;
-    // vr_label_*, vr_region_grow* (vr_label.h): the context's own labels (4 bytes per voxel of the
-    // box), the root table (vr_internal.h LabelScratch), the component records and vr_region_grow's
-    // device copy of the host mask; all grown on demand
-    void *label_dev = nullptr, *label_aux_dev = nullptr, *label_tab_dev = nullptr, *label_out_dev = nullptr;
-    size_t label_bytes = 0, label_aux_bytes = 0, label_tab_bytes = 0, label_out_bytes = 0;
-    // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
-    // taken while timing is enabled; 0 for a pass that call did not run
-    float label_pass_ms[kLabelPassSlots] = {};
-    // vr_render (host output): row bands rendered on two streams while finished bands copy
-    // to the host on a third, so the PCIe copy hides behind the rest of the frame
-    hipStream_t band_stream[2] = {nullptr, nullptr};
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t band_ev[kRenderBands] = {};
-    // timing
-    bool timing = false;
-    std::vector<hipEvent_t> ev_pool;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending;
-    double timed_ms = 0.0;
-    uint64_t timed_launches = 0;
-    // launch-policy overrides for tests and A/B experiments (include/vr/vr_debug.h); the
-    // product path never reads the process environment
-    struct Knobs {
-        int pipeline = -1, pair = -1, pair_lanes = 0, grad_field = -1, u8_layout = -1,
-            tile_order = 0, narrow = 1, alt = -1, mip_inflight = 0, field_order = -1, hist_agg = -1,
-            hit_inflight = -1;
-    } knobs;
-    // multi-device context (vr_create_mask): one member context per device of the mask, the
-    // volume/TF/slicing replicated on each, frames rendered across them by `group`
-    std::vector<vr_ctx *> members;
-    vr::Group *group = nullptr;
-    uint32_t device_mask = 0;
-    hipStream_t group_stream = nullptr;  // vr_render's frame stream (device 0)
-    // row blocks over ranks for vr_render_device (nranks > 1), vr_assemble_rows and every frame
-    // of a multi-device context (vr_set_row_share; vr_internal.h RowShare)
-    RowShare share{1, 1};
-    // device bytes the derived structures (difference field, alternative copies, skip-empty
-    // classification) may take together (vr_set_memory_budget): VR_MEMORY_BUDGET_DEFAULT
-    // (kDerivedBudgetBricks x the bricks), VR_MEMORY_BUDGET_UNLIMITED, or a byte count
-    uint64_t budget = VR_MEMORY_BUDGET_DEFAULT;
-    std::string err;
-};
 
 namespace {
-
 thread_local std::string g_err;
+}
+
+namespace vr {
 
 int fail(vr_ctx *c, int code, const std::string &msg)
 {
@@ -221,12 +37,6 @@ int hip_fail(vr_ctx *c, hipError_t e, const char *what)
     return fail(c, e == hipErrorOutOfMemory ? VR_ENOMEM : VR_EIO, m);
 }
 
-#define HIP_TRY(c, expr, what)                        \
-    do {                                              \
-        hipError_t _e = (expr);                       \
-        if (_e != hipSuccess) return hip_fail(c, _e, what); \
-    } while (0)
-
 // Resource swaps wait for the device first, as the reference does (vkDeviceWaitIdle,
 // offscreen_pass.cpp:242,260,282): a frame still in flight on any stream may read the volume,
 // TF or derived fields that are about to be rewritten or freed.
@@ -236,6 +46,68 @@ int wait_idle(vr_ctx *c)
     HIP_TRY(c, hipDeviceSynchronize(), "hipDeviceSynchronize (resource swap)");
     return VR_OK;
 }
+
+int check_params(vr_ctx *c, const vr_params *p)
+{
+    if (!p) return fail(c, VR_EINVAL, "params is NULL");
+    if (!(p->step > 0.0f) || !std::isfinite(p->step))
+        return fail(c, VR_EINVAL, "params.step must be a positive finite float");
+    if (!(p->ray_dist >= 0.0f) || !std::isfinite(p->ray_dist))
+        return fail(c, VR_EINVAL, "params.ray_dist must be finite and >= 0");
+    if (p->spec_power < 0 || p->spec_power > 256)
+        return fail(c, VR_EINVAL, "params.spec_power must be in [0, 256]");
+    if (p->frames_in_flight < 0 || p->frames_in_flight > 16)
+        return fail(c, VR_EINVAL, "params.frames_in_flight must be in [0, 16]");
+    if (p->exact_gradient != 0 && p->exact_gradient != 1)
+        return fail(c, VR_EINVAL, "params.exact_gradient must be 0 or 1");
+    if (p->depth_zero_to_one != 0 && p->depth_zero_to_one != 1)
+        return fail(c, VR_EINVAL, "params.depth_zero_to_one must be 0 or 1");
+    const float n = p->ray_dist / p->step;
+    if (n > 1.0e8f) return fail(c, VR_EINVAL, "params.ray_dist / step too large");
+    return VR_OK;
+}
+
+hipEvent_t pooled_event(vr_ctx *c)
+{
+    if (!c->ev_pool.empty()) {
+        hipEvent_t e = c->ev_pool.back();
+        c->ev_pool.pop_back();
+        return e;
+    }
+    // timing-only events: no system-scope fence when recorded.  The default event's fence
+    // writes back and invalidates the caches between this frame's kernel and the next one on
+    // the stream (C3 with 3 frames in flight: 5-10% per frame with timing on)
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
+    return e;
+}
+
+int reserve(vr_ctx *c, DevBlock &b, size_t need, const char *what, const char *idle_first)
+{
+    if (b.bytes >= need) return VR_OK;
+    if (idle_first) HIP_TRY(c, hipDeviceSynchronize(), idle_first);
+    if (b.p) hipFree(b.p);
+    b = DevBlock{};
+    HIP_TRY(c, hipMalloc(&b.p, need), what);
+    b.bytes = need;
+    return VR_OK;
+}
+
+int read_counters(vr_ctx *c, vr_stats *out)
+{
+    unsigned long long h[5];
+    HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
+    out->rays = h[0];
+    out->samples = h[1];
+    out->shaded_samples = h[2];
+    out->steps = h[3];
+    out->skipped_samples = h[4];
+    return VR_OK;
+}
+
+}  // namespace vr
+
+namespace {
 
 int storage_for(int dtype)
 {
@@ -508,12 +380,6 @@ int data_range(vr_ctx *c, hipStream_t s)
     uint32_t h[2];
     HIP_TRY(c, hipMemcpyAsync(h, mm, sizeof h, hipMemcpyDeviceToHost, s), "hipMemcpy(range)");
     HIP_TRY(c, hipStreamSynchronize(s), "data range sync");
-    auto unorder = [](uint32_t o) {
-        const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
     c->data_lo = unorder(h[0]);
     c->data_hi = unorder(h[1]);
     return VR_OK;
@@ -556,26 +422,6 @@ int upload_tf(vr_ctx *c, const uint32_t *tf, uint32_t n)
             "hipMemcpy(TF alpha prefix)");
     c->tf_n = n;
     c->dist_valid = false;
-    return VR_OK;
-}
-
-int check_params(vr_ctx *c, const vr_params *p)
-{
-    if (!p) return fail(c, VR_EINVAL, "params is NULL");
-    if (!(p->step > 0.0f) || !std::isfinite(p->step))
-        return fail(c, VR_EINVAL, "params.step must be a positive finite float");
-    if (!(p->ray_dist >= 0.0f) || !std::isfinite(p->ray_dist))
-        return fail(c, VR_EINVAL, "params.ray_dist must be finite and >= 0");
-    if (p->spec_power < 0 || p->spec_power > 256)
-        return fail(c, VR_EINVAL, "params.spec_power must be in [0, 256]");
-    if (p->frames_in_flight < 0 || p->frames_in_flight > 16)
-        return fail(c, VR_EINVAL, "params.frames_in_flight must be in [0, 16]");
-    if (p->exact_gradient != 0 && p->exact_gradient != 1)
-        return fail(c, VR_EINVAL, "params.exact_gradient must be 0 or 1");
-    if (p->depth_zero_to_one != 0 && p->depth_zero_to_one != 1)
-        return fail(c, VR_EINVAL, "params.depth_zero_to_one must be 0 or 1");
-    const float n = p->ray_dist / p->step;
-    if (n > 1.0e8f) return fail(c, VR_EINVAL, "params.ray_dist / step too large");
     return VR_OK;
 }
 
@@ -713,7 +559,9 @@ bool use_pair(const vr_ctx *c, const MarchParams &P, const vr_params *p)
            (ST_F32 | kAltFlag);
 }
 
-int build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
+}  // namespace
+
+int vr::build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
                  int out_format, uint32_t row_block, uint32_t rank, uint32_t nranks,
                  RowShare share, MarchParams &P)
 {
@@ -794,6 +642,8 @@ int build_params(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out,
     P.pipelined = use_pipeline(p->shading != 0, P.tiles_x * P.tiles_y, c);
     return VR_OK;
 }
+
+namespace {
 
 // After a build on `s`: frames on other streams wait for it (ensure_derived).
 // The frame fence of stream s (nullptr: none yet).
@@ -1607,16 +1457,6 @@ vr_ctx::TileSched *tile_sched(vr_ctx *c, MarchParams &P, void *stream, uint32_t 
 }
 
 // ---- multi-device contexts (vr_create_mask) ----
-bool is_group(const vr_ctx *c) { return c && c->group; }
-
-// Resource swaps on a multi-device context: every issued frame done on every device first.
-int group_idle(vr_ctx *c)
-{
-    std::string m;
-    if (vr::group_synchronize(c->group, &m) != VR_OK) return fail(c, VR_EIO, m);
-    return VR_OK;
-}
-
 // Member 0 holds the new volume: copy its bricks to every other member over xGMI (device to
 // device, one stream per destination, all in flight together), so each device renders from
 // its own replica (the volume replicated per GPU).
@@ -1656,13 +1496,6 @@ int replicate_volume(vr_ctx *c)
             hipStreamDestroy(st[k]);
         }
     hipSetDevice(c->device);
-    return rc;
-}
-
-// A member's failure reported on the multi-device context.
-int member_rc(vr_ctx *c, vr_ctx *m, int rc)
-{
-    if (rc != VR_OK) c->err = m->err;
     return rc;
 }
 
@@ -1716,21 +1549,6 @@ void knobs_from_env(vr_ctx *c)
         if (e[0] >= '1' && e[0] <= '4') c->knobs.tile_order = e[0] - '0';
 }
 #endif
-
-hipEvent_t pooled_event(vr_ctx *c)
-{
-    if (!c->ev_pool.empty()) {
-        hipEvent_t e = c->ev_pool.back();
-        c->ev_pool.pop_back();
-        return e;
-    }
-    // timing-only events: no system-scope fence when recorded.  The default event's fence
-    // writes back and invalidates the caches between this frame's kernel and the next one on
-    // the stream (C3 with 3 frames in flight: 5-10% per frame with timing on)
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
-    return e;
-}
 
 // A multi-device context over `devices` (member m on devices[m]; member 0 assembles).
 vr_ctx *create_members(const std::vector<int> &devices, uint32_t width, uint32_t height,
@@ -1984,14 +1802,9 @@ void vr_destroy(vr_ctx *c)
         hipFree(t.lists);
     }
     if (c->counters) hipFree(c->counters);
-    if (c->frame_dev) hipFree(c->frame_dev);
-    if (c->mpr_dev) hipFree(c->mpr_dev);
-    if (c->hit_dev) hipFree(c->hit_dev);
-    if (c->mesh_dev) hipFree(c->mesh_dev);
-    if (c->mesh_out_dev) hipFree(c->mesh_out_dev);
-    for (void *p : {c->label_dev, c->label_aux_dev, c->label_tab_dev, c->label_out_dev})
-        if (p) hipFree(p);
-    if (c->hist_dev) hipFree(c->hist_dev);
+    for (const DevBlock &b : {c->frame_dev, c->mpr_dev, c->hist_dev, c->hit_dev, c->mesh_dev, c->mesh_out_dev,
+                              c->label_dev, c->label_aux_dev, c->label_tab_dev, c->label_out_dev})
+        if (b.p) hipFree(b.p);
     for (auto e : c->band_ev)
         if (e) hipEventDestroy(e);
     for (auto st : c->band_stream)
@@ -2004,11 +1817,8 @@ int vr_resize(vr_ctx *c, uint32_t width, uint32_t height)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (width == 0 || height == 0) return VR_OK;  // offscreen_pass.cpp:237-239
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_resize(m, width, height)) return member_rc(c, m, rc);
-    }
+    if (is_group(c))
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_resize(m, width, height); })) return rc;
     c->width = width;
     c->height = height;
     return VR_OK;
@@ -2182,12 +1992,6 @@ int vr_generate_volume(vr_ctx *c, int kind, int dtype, uint32_t nx, uint32_t ny,
     }
     hipFree(lin);
     if (rc) return rc;
-    auto unorder = [](uint32_t o) {
-        const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
     c->storage = st;
     c->layout = lay;
     c->nx = nx;
@@ -2271,12 +2075,7 @@ int vr_set_transfer_function(vr_ctx *c, const uint32_t *rgba8_srgb, uint32_t n)
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (!rgba8_srgb || n == 0) return fail(c, VR_EINVAL, "transfer function is empty");
     if (n > (1u << 20)) return fail(c, VR_EINVAL, "transfer function too large");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_transfer_function(m, rgba8_srgb, n)) return member_rc(c, m, rc);
-        return VR_OK;
-    }
+    if (is_group(c)) return on_members(c, [&](vr_ctx *m) { return vr_set_transfer_function(m, rgba8_srgb, n); });
     if (int rc = wait_idle(c)) return rc;
     return upload_tf(c, rgba8_srgb, n);
 }
@@ -2285,11 +2084,8 @@ int vr_set_slicing(vr_ctx *c, const float min_slice[3], const float max_slice[3]
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (!min_slice || !max_slice) return fail(c, VR_EINVAL, "slice bounds are NULL");
-    if (is_group(c)) {  // frames already issued keep the old box (as the reference's UBO ring)
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_slicing(m, min_slice, max_slice)) return member_rc(c, m, rc);
-    }
+    if (is_group(c))  // frames already issued keep the old box (as the reference's UBO ring)
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_set_slicing(m, min_slice, max_slice); })) return rc;
     for (int a = 0; a < 3; ++a) {
         c->smin[a] = min_slice[a];
         c->smax[a] = max_slice[a];
@@ -2303,11 +2099,8 @@ int vr_set_render_mode(vr_ctx *c, int mode)
     if (mode != VR_MODE_COMPOSITE && mode != VR_MODE_MIP && mode != VR_MODE_ISO &&
         mode != VR_MODE_MINIP && mode != VR_MODE_MEAN)  // 2, 5: unassigned
         return fail(c, VR_EINVAL, "unknown render mode");
-    if (is_group(c)) {  // frames already issued keep the old mode (as the slice box)
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_render_mode(m, mode)) return member_rc(c, m, rc);
-    }
+    if (is_group(c))  // frames already issued keep the old mode (as the slice box)
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_set_render_mode(m, mode); })) return rc;
     c->render_mode = mode;
     return VR_OK;
 }
@@ -2323,11 +2116,8 @@ int vr_set_isovalue(vr_ctx *c, float v)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (!std::isfinite(v)) return fail(c, VR_EINVAL, "the isovalue is not finite");
-    if (is_group(c)) {  // frames already issued keep the old isovalue (as the mode)
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_isovalue(m, v)) return member_rc(c, m, rc);
-    }
+    if (is_group(c))  // frames already issued keep the old isovalue (as the mode)
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_set_isovalue(m, v); })) return rc;
     c->isovalue = v;
     return VR_OK;
 }
@@ -2356,11 +2146,9 @@ int vr_set_row_share(vr_ctx *c, uint32_t first_weight, uint32_t other_weight)
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (first_weight < 1 || other_weight < 1 || first_weight > 64 || other_weight > 64)
         return fail(c, VR_EINVAL, "row share weights must be in [1, 64]");
-    if (is_group(c)) {  // frames in flight keep their split; the pipelines are rebuilt
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_row_share(m, first_weight, other_weight)) return member_rc(c, m, rc);
-    }
+    if (is_group(c))  // frames in flight keep their split; the pipelines are rebuilt
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_set_row_share(m, first_weight, other_weight); }))
+            return rc;
     c->share = RowShare{first_weight, other_weight};
     return VR_OK;
 }
@@ -2377,9 +2165,7 @@ int vr_set_memory_budget(vr_ctx *c, uint64_t bytes)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (is_group(c)) {  // per device: every member holds its own replica's structures
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_memory_budget(m, bytes)) return member_rc(c, m, rc);
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_set_memory_budget(m, bytes); })) return rc;
         c->budget = bytes;
         return VR_OK;
     }
@@ -2413,9 +2199,7 @@ int vr_prepare(vr_ctx *c, const vr_camera *cam, const vr_params *p)
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_prepare(m, cam, p)) return member_rc(c, m, rc);
+        if (int rc = on_members(c, [&](vr_ctx *m) { return vr_prepare(m, cam, p); })) return rc;
         hipSetDevice(c->device);
         return VR_OK;
     }
@@ -2524,14 +2308,8 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
     FrameVariant v;  // VF_NONE where no kernel serves the facts: launch_frame then fails
     resolve_variant(launch_facts(c, p, P, layout, false), &v);
     vr_ctx::TileSched *ts = tile_sched(c, P, stream, variant_tile_key(v, layout));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timing = c->timing;  // read once: the pair is recorded and queued together
-    if (timing) {
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-    }
+    Interval timed;
+    if (int rc = timed.begin(c, s)) return rc;
     HIP_TRY(c, launch_frame(v, P, M, iso_args(c, p, M), s),
             v.family == VF_ISO    ? "iso kernel launch"
             : v.family == VF_PROJ ? "proj kernel launch"
@@ -2539,10 +2317,7 @@ int render_device_impl(vr_ctx *c, const vr_camera *cam, const vr_params *p, void
                                   : "march kernel launch");
     c->last_variant = v;
     c->last_mpr_name.clear();
-    if (timing) {
-        HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-        c->ev_pending.emplace_back(e0, e1);
-    }
+    if (int rc = timed.end()) return rc;
     // next launches of this geometry: longest tiles first, re-ordered every kReorderEvery
     // launches (the order kernel runs after the timed frame kernel, inside the frame)
     if (ts && ts->launches++ % kReorderEvery == 0) {
@@ -2565,20 +2340,14 @@ int vr_render(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out, in
     const uint32_t W = c->width, H = c->height;
     if (is_group(c)) {  // the frame across the devices into device 0, then one copy out
         const size_t fb = (size_t)W * H * bpp;
-        if (c->frame_bytes < fb) {
-            if (c->frame_dev) hipFree(c->frame_dev);
-            c->frame_dev = nullptr;
-            c->frame_bytes = 0;
-            HIP_TRY(c, hipMalloc(&c->frame_dev, fb), "hipMalloc(frame)");
-            c->frame_bytes = fb;
-        }
+        if (int rc = reserve(c, c->frame_dev, fb, "hipMalloc(frame)", nullptr)) return rc;
         if (!c->group_stream)
             HIP_TRY(c, hipStreamCreateWithFlags(&c->group_stream, hipStreamNonBlocking),
                     "hipStreamCreate");
-        int rc = vr_render_device(c, cam, p, c->frame_dev, out_format, vr::kGroupRowBlock, 0, 1,
+        int rc = vr_render_device(c, cam, p, c->frame_dev.p, out_format, vr::kGroupRowBlock, 0, 1,
                                   c->group_stream);
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpyAsync(out, c->frame_dev, fb, hipMemcpyDeviceToHost, c->group_stream),
+        HIP_TRY(c, hipMemcpyAsync(out, c->frame_dev.p, fb, hipMemcpyDeviceToHost, c->group_stream),
                 "hipMemcpyAsync(frame)");
         HIP_TRY(c, hipStreamSynchronize(c->group_stream), "hipStreamSynchronize(frame)");
         return VR_OK;
@@ -2588,18 +2357,12 @@ int vr_render(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out, in
     const int nb = H >= kHostBandMinRows ? kRenderBands : 1;
     const uint32_t R = nb == 1 ? 16 : ((H + nb - 1) / nb + 15) / 16 * 16;
     const size_t bytes = (size_t)W * (nb == 1 ? H : (size_t)R * nb) * bpp;
-    if (c->frame_bytes < bytes) {
-        if (c->frame_dev) hipFree(c->frame_dev);
-        c->frame_dev = nullptr;
-        c->frame_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->frame_dev, bytes), "hipMalloc(frame)");
-        c->frame_bytes = bytes;
-    }
+    if (int rc = reserve(c, c->frame_dev, bytes, "hipMalloc(frame)", nullptr)) return rc;
     if (nb == 1) {
-        int rc = render_device_impl(c, cam, p, c->frame_dev, out_format, 16, 0, 1, RowShare{1, 1},
+        int rc = render_device_impl(c, cam, p, c->frame_dev.p, out_format, 16, 0, 1, RowShare{1, 1},
                                     nullptr);
         if (rc) return rc;
-        HIP_TRY(c, hipMemcpy(out, c->frame_dev, (size_t)W * H * bpp, hipMemcpyDeviceToHost),
+        HIP_TRY(c, hipMemcpy(out, c->frame_dev.p, (size_t)W * H * bpp, hipMemcpyDeviceToHost),
                 "hipMemcpy(frame)");
         return VR_OK;
     }
@@ -2618,7 +2381,7 @@ int vr_render(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out, in
     for (int b = 0; b < nb; ++b) {
         hipStream_t s = c->band_stream[b & 1];
         int rc = render_device_impl(c, cam, &pb,
-                                    static_cast<char *>(c->frame_dev) + (size_t)b * R * W * bpp,
+                                    static_cast<char *>(c->frame_dev.p) + (size_t)b * R * W * bpp,
                                     out_format, R, (uint32_t)b, (uint32_t)nb, RowShare{1, 1}, s);
         if (rc) return rc;
         HIP_TRY(c, hipEventRecord(c->band_ev[b], s), "hipEventRecord(band)");
@@ -2631,7 +2394,7 @@ int vr_render(vr_ctx *c, const vr_camera *cam, const vr_params *p, void *out, in
         const size_t rows = std::min<size_t>(R, H - row0);
         HIP_TRY(c, hipStreamWaitEvent(c->copy_stream, c->band_ev[b], 0), "hipStreamWaitEvent(band)");
         HIP_TRY(c, hipMemcpyAsync(static_cast<char *>(out) + row0 * W * bpp,
-                                  static_cast<char *>(c->frame_dev) + row0 * W * bpp,
+                                  static_cast<char *>(c->frame_dev.p) + row0 * W * bpp,
                                   rows * W * bpp, hipMemcpyDeviceToHost, c->copy_stream),
                 "hipMemcpyAsync(band)");
     }
@@ -2720,24 +2483,15 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
 {
     if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     if (!out) return fail(c, VR_EINVAL, "stats is NULL");
-    if (is_group(c)) {  // every device holds the same scene: count on member 0
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_count_work(c->members[0], cam, p, row_block, rank, nranks, out));
-    }
+    if (is_group(c))
+        return on_replica(c, [&](vr_ctx *m) { return vr_count_work(m, cam, p, row_block, rank, nranks, out); });
     HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
     const size_t bytes = (size_t)c->width *
                          share_shard_rows(c->height, row_block ? row_block : 1, nranks ? nranks : 1,
                                           c->share) * 4;
-    if (c->frame_bytes < bytes) {
-        if (c->frame_dev) hipFree(c->frame_dev);
-        c->frame_dev = nullptr;
-        c->frame_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->frame_dev, bytes), "hipMalloc(frame)");
-        c->frame_bytes = bytes;
-    }
+    if (int rc = reserve(c, c->frame_dev, bytes, "hipMalloc(frame)", nullptr)) return rc;
     MarchParams P;
-    int rc = build_params(c, cam, p, c->frame_dev, VR_OUT_RGBA8, row_block, rank, nranks,
+    int rc = build_params(c, cam, p, c->frame_dev.p, VR_OUT_RGBA8, row_block, rank, nranks,
                           c->share, P);
     if (rc) return rc;
     uint32_t refused = 0;  // a count is not a frame: not a downgrade
@@ -2763,14 +2517,7 @@ int vr_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, uint32_t 
                                   : "march (count) launch");
     c->last_variant = v;
     c->last_mpr_name.clear();
-    unsigned long long h[5];
-    HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
-    out->rays = h[0];
-    out->samples = h[1];
-    out->shaded_samples = h[2];
-    out->steps = h[3];
-    out->skipped_samples = h[4];
-    return VR_OK;
+    return read_counters(c, out);
 }
 
 int vr_timing_enable(vr_ctx *c, int enable)
@@ -2966,1076 +2713,6 @@ int vr_debug_get_knob(const vr_ctx *c, int knob, int *value)
     int *k = knob_slot(const_cast<vr_ctx *>(c), knob);
     if (!k) return fail(nullptr, VR_EINVAL, "unknown knob");
     *value = *k;
-    return VR_OK;
-}
-
-}  // extern "C"
-
-// ---- multi-planar reformat (include/vr/vr_mpr.h) ---------------------------------------------
-namespace {
-// the plane's own errors (vr_mpr.h); c may be NULL (vr_mpr_axis_plane)
-int check_plane_shape(vr_ctx *c, uint32_t width, uint32_t height, uint32_t nsamples, int op)
-{
-    if (width == 0 || height == 0) return fail(c, VR_EINVAL, "mpr image size must be non-zero");
-    if ((unsigned long long)((width + 15ull) / 16) * ((height + 15ull) / 16) >= 1ull << 31)
-        return fail(c, VR_EINVAL, "mpr image too large");
-    if (nsamples == 0 || nsamples > VR_MPR_MAX_SAMPLES)
-        return fail(c, VR_EINVAL, "mpr nsamples must be in [1, 4096]");
-    if (op != VR_MPR_MAX && op != VR_MPR_MIN && op != VR_MPR_MEAN)
-        return fail(c, VR_EINVAL, "unknown mpr op");
-    return VR_OK;
-}
-
-// Everything vr_mpr.h refuses, then the kernel's argument; c is a single-device context.
-int build_mpr(vr_ctx *c, const vr_mpr_plane *pl, const vr_params *p, void *out, int out_format,
-              MprArgs &A)
-{
-    if (!pl) return fail(c, VR_EINVAL, "plane is NULL");
-    if (int rc = check_params(c, p)) return rc;
-    for (int a = 0; a < 3; ++a)
-        if (!std::isfinite(pl->origin[a]) || !std::isfinite(pl->du[a]) || !std::isfinite(pl->dv[a]) ||
-            !std::isfinite(pl->dn[a]))
-            return fail(c, VR_EINVAL, "mpr plane vectors must be finite");
-    if (int rc = check_plane_shape(c, pl->width, pl->height, pl->nsamples, pl->op)) return rc;
-    if (out_format != VR_OUT_RGBA8 && out_format != VR_OUT_RGBA32F)
-        return fail(c, VR_EINVAL, "unknown out_format");
-    std::memset(&A, 0, sizeof(A));
-    A.vol = c->bricks;
-    A.vol_bytes = c->brick_bytes;
-    A.tf = c->tf;
-    A.out = out;
-    A.counters = c->counters;
-    for (int a = 0; a < 3; ++a) {
-        A.origin[a] = (double)pl->origin[a];
-        A.du[a] = (double)pl->du[a];
-        A.dv[a] = (double)pl->dv[a];
-        A.dn[a] = (double)pl->dn[a];
-        A.smin[a] = c->smin[a];
-        A.smax[a] = c->smax[a];
-    }
-    A.half_w = 0.5 * (double)pl->width;
-    A.half_h = 0.5 * (double)pl->height;
-    A.half_n = 0.5 * (double)(pl->nsamples - 1);
-    A.nbx = bricks_for(c->nx, 0, c->layout);
-    A.nby = bricks_for(c->ny, 1, c->layout);
-    A.fnx = (float)c->nx;
-    A.fny = (float)c->ny;
-    A.fnz = (float)c->nz;
-    A.vmin = c->vmin;
-    A.range = c->vmax - c->vmin;
-    // (the frames' reciprocal division domain, build_params)
-    A.div_fast = A.range >= 0x1p-40f && A.range < 0x1p100f && std::fabs(c->vmin) < 0x1p100f &&
-                 std::fabs(c->vmax) < 0x1p100f;
-    A.inv_range = A.div_fast ? 1.0f / A.range : 0.0f;
-    A.tf_n = (int32_t)c->tf_n;
-    A.tf_nf = (float)c->tf_n;
-    for (int k = 0; k < 4; ++k) A.clear[k] = p->clear_color[k];
-    A.W = pl->width;
-    A.H = pl->height;
-    A.nsamples = pl->nsamples;
-    A.tiles_x = (pl->width + 15) / 16;
-    A.tiles_y = (pl->height + 15) / 16;
-    A.tile_order = c->knobs.tile_order == 1 || c->knobs.tile_order == 3 ? (uint32_t)c->knobs.tile_order
-                                                                         : kMprTileOrder(pl->nsamples);
-    A.supers_x = (A.tiles_x + kSuper - 1) / kSuper;
-    A.supers_total = A.supers_x * ((A.tiles_y + kSuper - 1) / kSuper);
-    A.out_format = out_format;
-    A.op = pl->op;
-    A.out_bytes = (unsigned long long)pl->width * pl->height * (out_format == VR_OUT_RGBA32F ? 16 : 4);
-    return VR_OK;
-}
-
-// The MPR launch on `stream`, bracketed by the timing events like a frame kernel.  It reads the
-// base bricks and the TF only (a swap of either waits for the device first), so it takes part in
-// no build, eviction or frame fence.
-int mpr_render_device_impl(vr_ctx *c, const vr_mpr_plane *pl, const vr_params *p, void *out_dev,
-                           int out_format, void *stream)
-{
-    MprArgs A;
-    if (int rc = build_mpr(c, pl, p, out_dev, out_format, A)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timing = c->timing;
-    if (timing) {
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-    }
-    std::string name;
-    HIP_TRY(c, launch_mpr(c->layout, false, A, s, &name), "mpr kernel launch");
-    c->last_mpr_name = name;
-    if (timing) {
-        HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-        c->ev_pending.emplace_back(e0, e1);
-    }
-    return VR_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int vr_mpr_render_device(vr_ctx *c, const vr_mpr_plane *pl, const vr_params *p, void *out_dev,
-                         int out_format, void *stream)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!out_dev) return fail(c, VR_EINVAL, "output buffer is NULL");
-    if (is_group(c)) {  // the whole image on the lowest device, which holds a replica
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_mpr_render_device(c->members[0], pl, p, out_dev, out_format, stream));
-    }
-    return mpr_render_device_impl(c, pl, p, out_dev, out_format, stream);
-}
-
-int vr_mpr_render(vr_ctx *c, const vr_mpr_plane *pl, const vr_params *p, void *out, int out_format)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!out) return fail(c, VR_EINVAL, "output buffer is NULL");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_mpr_render(c->members[0], pl, p, out, out_format));
-    }
-    MprArgs A;  // the argument checks, before the staging image is sized by the plane
-    if (int rc = build_mpr(c, pl, p, out, out_format, A)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t bytes = (size_t)A.out_bytes;
-    if (c->mpr_bytes < bytes) {
-        if (c->mpr_dev) hipFree(c->mpr_dev);  // (its last image was copied out synchronously)
-        c->mpr_dev = nullptr;
-        c->mpr_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->mpr_dev, bytes), "hipMalloc(mpr image)");
-        c->mpr_bytes = bytes;
-    }
-    if (int rc = mpr_render_device_impl(c, pl, p, c->mpr_dev, out_format, nullptr)) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->mpr_dev, bytes, hipMemcpyDeviceToHost), "hipMemcpy(mpr image)");
-    return VR_OK;
-}
-
-int vr_mpr_count_work(vr_ctx *c, const vr_mpr_plane *pl, const vr_params *p, vr_stats *out)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!out) return fail(c, VR_EINVAL, "stats is NULL");
-    if (is_group(c)) {  // every device holds the same scene: count on member 0
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_mpr_count_work(c->members[0], pl, p, out));
-    }
-    MprArgs A;  // (the counting kernel writes no pixel: no output, any format)
-    if (int rc = build_mpr(c, pl, p, nullptr, VR_OUT_RGBA8, A)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
-    std::string name;
-    HIP_TRY(c, launch_mpr(c->layout, true, A, nullptr, &name), "mpr (count) launch");
-    c->last_mpr_name = name;
-    unsigned long long h[5];
-    HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
-    out->rays = h[0];
-    out->samples = h[1];
-    out->shaded_samples = h[2];
-    out->steps = h[3];
-    out->skipped_samples = h[4];
-    return VR_OK;
-}
-
-int vr_mpr_axis_plane(int axis, float position, uint32_t width, uint32_t height, uint32_t nsamples,
-                      float spacing, int op, vr_mpr_plane *out)
-{
-    if (!out) return fail(nullptr, VR_EINVAL, "plane is NULL");
-    if (axis < 0 || axis > 2) return fail(nullptr, VR_EINVAL, "mpr axis must be 0, 1 or 2");
-    if (!std::isfinite(position) || !std::isfinite(spacing))
-        return fail(nullptr, VR_EINVAL, "mpr position and spacing must be finite");
-    if (int rc = check_plane_shape(nullptr, width, height, nsamples, op)) return rc;
-    vr_mpr_plane pl;
-    std::memset(&pl, 0, sizeof pl);
-    for (int a = 0; a < 3; ++a) pl.origin[a] = a == axis ? position : 0.5f;
-    pl.dn[axis] = spacing;
-    const float ru = 1.0f / (float)width, rv = 1.0f / (float)height;
-    if (axis == 2) {  // axial: right +x, down +y
-        pl.du[0] = ru;
-        pl.dv[1] = rv;
-    } else {  // coronal: right +x; sagittal: right +y; both down -z (world +z is screen-up)
-        pl.du[axis == 1 ? 0 : 1] = ru;
-        pl.dv[2] = -rv;
-    }
-    pl.width = width;
-    pl.height = height;
-    pl.nsamples = nsamples;
-    pl.op = op;
-    *out = pl;
-    return VR_OK;
-}
-
-// ---- value histogram and value window (include/vr/vr_hist.h) ---------------------------------
-
-int vr_hist_edges(float lo, float hi, uint32_t nbins, float *edges_out)
-{
-    if (!edges_out) return fail(nullptr, VR_EINVAL, "edges is NULL");
-    if (!hist_range_ok(lo, hi, nbins))
-        return fail(nullptr, VR_EINVAL, "histogram needs finite lo < hi and 1 <= nbins <= 4096");
-    hist_edges(lo, hi, nbins, edges_out);
-    return VR_OK;
-}
-
-int vr_hist_window(const uint64_t *bins, uint32_t nbins, float lo, float hi, double p_lo,
-                   double p_hi, float *vmin_out, float *vmax_out)
-{
-    if (!hist_window(bins, nbins, lo, hi, p_lo, p_hi, vmin_out, vmax_out))
-        return fail(nullptr, VR_EINVAL,
-                    "histogram window needs bins with a count, finite lo < hi, 1 <= nbins <= 4096 "
-                    "and 0 <= p_lo < p_hi <= 1");
-    return VR_OK;
-}
-
-int vr_histogram(vr_ctx *c, const vr_hist_request *req, uint64_t *bins_host, vr_hist_info *info)
-{
-    if (!c || !req || !bins_host || !info) return fail(c, VR_EINVAL, "NULL argument");
-    if (!hist_range_ok(req->lo, req->hi, req->nbins))
-        return fail(c, VR_EINVAL, "histogram needs finite lo < hi and 1 <= nbins <= 4096");
-    if (req->use_box > 1) return fail(c, VR_EINVAL, "histogram use_box must be 0 or 1");
-    if (is_group(c)) {  // on the lowest device, which holds a replica
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_histogram(c->members[0], req, bins_host, info));
-    }
-    if (!c->bricks) return fail(c, VR_EINVAL, "no volume");
-    const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-    HistArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.nwork = 1;
-    for (int a = 0; a < 3; ++a) {
-        A.box_min[a] = req->use_box ? req->box_min[a] : 0u;
-        A.box_max[a] = req->use_box ? req->box_max[a] : dims[a];
-        if (A.box_min[a] >= A.box_max[a] || A.box_max[a] > dims[a])
-            return fail(c, VR_EINVAL, "histogram box is empty or beyond the volume");
-        // the bricks of padded indices box_min + kPad .. box_max - 1 + kPad
-        const uint32_t cells = (uint32_t)brick_cells(c->layout, a);
-        A.b0[a] = (A.box_min[a] + kPad) / cells;
-        A.nb[a] = (A.box_max[a] - 1 + kPad) / cells - A.b0[a] + 1;
-        A.nwork *= A.nb[a];
-    }
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t out_bytes = kHistOutWords * sizeof(unsigned long long);
-    if (!c->hist_dev)
-        HIP_TRY(c, hipMalloc(&c->hist_dev, out_bytes + kHistMaxBins * sizeof(float)),
-                "hipMalloc(histogram)");
-    float edges[kHistMaxBins];
-    hist_edges(req->lo, req->hi, req->nbins, edges);
-    A.vol = c->bricks;
-    A.out = static_cast<unsigned long long *>(c->hist_dev);
-    A.edges = reinterpret_cast<const float *>(static_cast<char *>(c->hist_dev) + out_bytes);
-    A.scale = hist_scale(req->lo, req->hi, req->nbins);
-    A.lo = req->lo;
-    A.hi = req->hi;
-    A.nbins = req->nbins;
-    A.nbx = bricks_for(c->nx, 0, c->layout);
-    A.nby = bricks_for(c->ny, 1, c->layout);
-    HIP_TRY(c, hipMemcpy(const_cast<float *>(A.edges), edges, req->nbins * sizeof(float),
-                         hipMemcpyHostToDevice), "hipMemcpy(histogram edges)");
-    HIP_TRY(c, hipMemsetAsync(A.out, 0, out_bytes, nullptr), "hipMemset(histogram)");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timing = c->timing;
-    if (timing) {
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, nullptr), "hipEventRecord");
-    }
-    std::string name;
-    // The kernel form (knob VR_KNOB_HIST_AGG overrides).  Plain 8-bit bricks count raw codes, and
-    // there a constant volume -- every lane on one LDS word -- takes 4.0x the Gaussians' time unless
-    // the wave's leading code is added once (C4: 3.53 -> 1.07 ms, the Gaussians 0.87 -> 1.14 ms);
-    // the other layouts bin every voxel first, the constant volume costs them 16 % and the
-    // aggregation 10 % on the Gaussians (C3: 0.51 / 0.59 ms against 0.56 / 0.55 ms), so they add
-    // singly (profiles/r15/hist/).
-    const bool agg = c->knobs.hist_agg >= 0 ? c->knobs.hist_agg == 1 : byte_storage(c->layout);
-    HIP_TRY(c, launch_hist(c->layout, agg, A, nullptr, &name), "histogram kernel launch");
-    c->last_mpr_name = name;
-    if (timing) {
-        HIP_TRY(c, hipEventRecord(e1, nullptr), "hipEventRecord");
-        c->ev_pending.emplace_back(e0, e1);
-    }
-    std::vector<unsigned long long> h((size_t)req->nbins + 4);
-    HIP_TRY(c, hipMemcpy(h.data(), A.out, ((size_t)req->nbins + 4) * sizeof(unsigned long long),
-                         hipMemcpyDeviceToHost), "hipMemcpy(histogram)");
-    vr_hist_info I;
-    std::memset(&I, 0, sizeof I);
-    I.below = h[req->nbins + 0];
-    I.above = h[req->nbins + 1];
-    I.nan = h[req->nbins + 2];
-    I.voxels = I.below + I.above + I.nan;
-    for (uint32_t b = 0; b < req->nbins; ++b) {
-        bins_host[b] = h[b];
-        I.voxels += h[b];
-    }
-    auto unorder = [](uint32_t o) {
-        const uint32_t u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    uint32_t ext[2];
-    std::memcpy(ext, &h[req->nbins + 3], sizeof ext);
-    const bool any = I.voxels > I.nan;
-    I.vmin = any ? unorder(~ext[0]) : INFINITY;
-    I.vmax = any ? unorder(ext[1]) : -INFINITY;
-    *info = I;
-    return VR_OK;
-}
-
-int vr_set_value_range(vr_ctx *c, float vmin, float vmax)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        for (vr_ctx *m : c->members)
-            if (int rc = vr_set_value_range(m, vmin, vmax)) return member_rc(c, m, rc);
-        return VR_OK;
-    }
-    // a frame in flight may read the distance field the next skip_empty frame rebuilds
-    if (int rc = wait_idle(c)) return rc;
-    c->vmin = vmin;
-    c->vmax = vmax;
-    c->dist_valid = false;  // built from vmin and range; the brick ranges and the fields stay
-    return VR_OK;
-}
-
-}  // extern "C"
-
-// ---- hit records and picking (include/vr/vr_hit.h) -------------------------------------------
-namespace {
-// What vr_hit.h refuses before it looks at the context: the NULL arguments and the request's own
-// fields (csrc/vr_hit_host.h); no HIP call.
-int check_hit_request(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-                      const void *out)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!cam || !p || !req || !out) return fail(c, VR_EINVAL, "NULL argument");
-    if (const char *m = hit_kind_error(req->kind, req->threshold)) return fail(c, VR_EINVAL, m);
-    if (req->use_rect > 1) return fail(c, VR_EINVAL, "hit use_rect must be 0 or 1");
-    return VR_OK;
-}
-
-// The kernel arguments of rectangle r; c is a single-device context.  build_params does the
-// camera and parameter checks and the ray constants of the whole framebuffer; the rectangle then
-// replaces the image the tiles cover (vr_internal.h HitArgs).  The view facts build_params notes
-// for the next frame's policy are put back: a hit image is no frame.
-int build_hit(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-              const HitRect &r, void *out, MarchParams &P, HitArgs &A)
-{
-    const bool dense_rows = c->dense_rows;
-    const double pixel_span = c->pixel_span, axis_align = c->axis_align, row_align = c->row_align;
-    const int ray_axis = c->ray_axis;
-    const int rc = build_params(c, cam, p, nullptr, VR_OUT_RGBA8, 16, 0, 1, RowShare{1, 1}, P);
-    c->dense_rows = dense_rows;
-    c->pixel_span = pixel_span;
-    c->axis_align = axis_align;
-    c->row_align = row_align;
-    c->ray_axis = ray_axis;
-    if (rc) return rc;
-    if ((unsigned long long)((r.w + 15ull) / 16) * ((r.h + kMarchRows - 1ull) / kMarchRows) >= 1ull << 31)
-        return fail(c, VR_EINVAL, "hit rectangle too large");
-    P.W = r.w;
-    P.H = r.h;
-    P.local_rows = r.h;
-    P.out_bytes = 0;
-    P.tiles_x = (r.w + 15) / 16;
-    P.tiles_y = (r.h + kMarchRows - 1) / kMarchRows;
-    P.tile_order = 3;  // the static super-tiles: the adaptive order's cost table is the frames'
-    P.supers_x = (P.tiles_x + kSuper - 1) / kSuper;
-    P.supers_total = P.supers_x * ((P.tiles_y + kSuper - 1) / kSuper);
-    P.pipelined = 0;
-    A.out = out;
-    A.out_bytes = hit_bytes(r);
-    A.threshold = req->threshold;
-    A.iso = c->isovalue;
-    A.x0 = r.x0;
-    A.y0 = r.y0;
-    return VR_OK;
-}
-
-int hit_inflight(const vr_ctx *c, int kind)
-{
-    return c->knobs.hit_inflight == 1 || c->knobs.hit_inflight == 2 ? c->knobs.hit_inflight
-                                                                      : kHitDefaultInFlight(kind);
-}
-
-// The hit launch on `stream`, bracketed by the timing events like a frame kernel.  It reads the
-// base bricks and the TF only (a swap of either waits for the device first), so it takes part in
-// no build, eviction or frame fence.
-int hit_launch(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-               const HitRect &r, void *out_dev, hipStream_t s)
-{
-    MarchParams P;
-    HitArgs A;
-    if (int rc = build_hit(c, cam, p, req, r, out_dev, P, A)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    const bool timing = c->timing;
-    if (timing) {
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-    }
-    std::string name;
-    HIP_TRY(c, launch_hit(c->layout, req->kind, false, hit_inflight(c, req->kind), P, A, s, &name),
-            "hit kernel launch");
-    c->last_mpr_name = name;
-    if (timing) {
-        HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-        c->ev_pending.emplace_back(e0, e1);
-    }
-    return VR_OK;
-}
-
-// The synchronous calls: the records of r through the context's own device buffer into out.
-int hit_to_host(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-                const HitRect &r, vr_hit *out)
-{
-    {  // the camera and parameter checks, before the buffer is sized by the rectangle
-        MarchParams P;
-        HitArgs A;
-        if (int rc = build_hit(c, cam, p, req, r, nullptr, P, A)) return rc;
-    }
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t bytes = (size_t)hit_bytes(r);
-    if (c->hit_bytes < bytes) {
-        if (c->hit_dev) hipFree(c->hit_dev);  // (its last records were copied out synchronously)
-        c->hit_dev = nullptr;
-        c->hit_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->hit_dev, bytes), "hipMalloc(hit records)");
-        c->hit_bytes = bytes;
-    }
-    if (int rc = hit_launch(c, cam, p, req, r, c->hit_dev, nullptr)) return rc;
-    HIP_TRY(c, hipMemcpy(out, c->hit_dev, bytes, hipMemcpyDeviceToHost), "hipMemcpy(hit records)");
-    return VR_OK;
-}
-}  // namespace
-
-extern "C" {
-
-int vr_hit_render_device(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-                         void *out_dev, void *stream)
-{
-    if (int rc = check_hit_request(c, cam, p, req, out_dev)) return rc;
-    if (is_group(c)) {  // on the lowest device, which holds a replica
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_hit_render_device(c->members[0], cam, p, req, out_dev, stream));
-    }
-    HitRect r;
-    if (const char *m = hit_rect_resolve(req->use_rect, req->rect, c->width, c->height, &r))
-        return fail(c, VR_EINVAL, m);
-    return hit_launch(c, cam, p, req, r, out_dev, static_cast<hipStream_t>(stream));
-}
-
-int vr_hit_render(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-                  vr_hit *out)
-{
-    if (int rc = check_hit_request(c, cam, p, req, out)) return rc;
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_hit_render(c->members[0], cam, p, req, out));
-    }
-    HitRect r;
-    if (const char *m = hit_rect_resolve(req->use_rect, req->rect, c->width, c->height, &r))
-        return fail(c, VR_EINVAL, m);
-    return hit_to_host(c, cam, p, req, r, out);
-}
-
-int vr_pick(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-            uint32_t px, uint32_t py, vr_hit *out)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!cam || !p || !req || !out) return fail(c, VR_EINVAL, "NULL argument");
-    // (the request's rectangle is ignored, use_rect with it)
-    if (const char *m = hit_kind_error(req->kind, req->threshold)) return fail(c, VR_EINVAL, m);
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_pick(c->members[0], cam, p, req, px, py, out));
-    }
-    HitRect r;
-    if (const char *m = hit_pick_resolve(px, py, c->width, c->height, &r)) return fail(c, VR_EINVAL, m);
-    return hit_to_host(c, cam, p, req, r, out);
-}
-
-int vr_hit_count_work(vr_ctx *c, const vr_camera *cam, const vr_params *p, const vr_hit_request *req,
-                      vr_stats *out)
-{
-    if (int rc = check_hit_request(c, cam, p, req, out)) return rc;
-    if (is_group(c)) {  // every device holds the same scene: count on member 0
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_hit_count_work(c->members[0], cam, p, req, out));
-    }
-    HitRect r;
-    if (const char *m = hit_rect_resolve(req->use_rect, req->rect, c->width, c->height, &r))
-        return fail(c, VR_EINVAL, m);
-    MarchParams P;
-    HitArgs A;  // (the counting kernel writes no record)
-    if (int rc = build_hit(c, cam, p, req, r, nullptr, P, A)) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    HIP_TRY(c, hipMemset(c->counters, 0, 8 * sizeof(unsigned long long)), "hipMemset(counters)");
-    std::string name;
-    HIP_TRY(c, launch_hit(c->layout, req->kind, true, 1, P, A, nullptr, &name), "hit (count) launch");
-    c->last_mpr_name = name;
-    unsigned long long h[5];
-    HIP_TRY(c, hipMemcpy(h, c->counters, sizeof(h), hipMemcpyDeviceToHost), "hipMemcpy(counters)");
-    out->rays = h[0];
-    out->samples = h[1];
-    out->shaded_samples = h[2];
-    out->steps = h[3];
-    out->skipped_samples = h[4];
-    return VR_OK;
-}
-
-}  // extern "C"
-
-// ---- connected components and region growing (include/vr/vr_label.h) ---------------------------
-namespace {
-// What vr_label.h refuses before it looks at the context: the NULL arguments and the request's own
-// fields (csrc/vr_label_host.h); no HIP call.
-int check_label_request(vr_ctx *c, const vr_label_request *req, const void *a, const void *b, const void *d)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!req || !a || !b || !d) return fail(c, VR_EINVAL, "NULL argument");
-    if (const char *m = label_request_error(req->lo, req->hi, req->connectivity, req->use_box))
-        return fail(c, VR_EINVAL, m);
-    return VR_OK;
-}
-
-// A context block of at least `need` bytes (grown on demand; an earlier call's passes may still
-// read the old block on another stream, so the device is idle before it is freed).
-int label_block(vr_ctx *c, void *&dev, size_t &have, size_t need, const char *what)
-{
-    if (have >= need && dev) return VR_OK;
-    HIP_TRY(c, hipDeviceSynchronize(), "hipDeviceSynchronize (label scratch)");
-    if (dev) hipFree(dev);
-    dev = nullptr;
-    have = 0;
-    HIP_TRY(c, hipMalloc(&dev, need), what);
-    have = need;
-    return VR_OK;
-}
-
-// One call's passes on stream s; c is a single-device context.  The timing events bracket the
-// labelling passes as one interval, the table passes as another and a region grow's mask pass as a
-// third (the copies of the counts to the host and the host's waits lie between them).
-struct LabelRun {
-    vr_ctx *c;
-    hipStream_t s;
-    LabelArgs A;
-    LabelBox box;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-
-    int begin()
-    {
-        if (!c->timing) return VR_OK;
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-        return VR_OK;
-    }
-    int end()
-    {
-        if (e0 && e1) {
-            HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-            c->ev_pending.emplace_back(e0, e1);
-            last0 = e0;
-            last1 = e1;
-        }
-        e0 = e1 = nullptr;
-        return VR_OK;
-    }
-    // Per-pass times for vr_debug_label_pass_ms (timing enabled only): an event after every pass
-    // but an interval's last, whose end is the interval's own e1; read by passes_read after the
-    // call's wait for the stream.  The interval itself stays one pair in ev_pending.
-    hipEvent_t last0 = nullptr, last1 = nullptr;
-    std::vector<std::pair<int, hipEvent_t>> marks;  // (the slot that ended, the event after it)
-    int mark(int slot)
-    {
-        if (!e0) return VR_OK;
-        hipEvent_t e = pooled_event(c);
-        if (!e) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e, s), "hipEventRecord");
-        marks.emplace_back(slot, e);
-        return VR_OK;
-    }
-    // after end() and a wait for s: the slots of `marks`, then last_slot up to the interval's end
-    int passes_read(int last_slot)
-    {
-        if (!last0 || !last1) return VR_OK;
-        hipEvent_t from = last0;
-        for (auto &m : marks) {
-            HIP_TRY(c, hipEventElapsedTime(&c->label_pass_ms[m.first], from, m.second), "hipEventElapsedTime");
-            if (from != last0) c->ev_pool.push_back(from);
-            from = m.second;
-        }
-        HIP_TRY(c, hipEventElapsedTime(&c->label_pass_ms[last_slot], from, last1), "hipEventElapsedTime");
-        if (from != last0) c->ev_pool.push_back(from);
-        marks.clear();
-        last0 = last1 = nullptr;
-        return VR_OK;
-    }
-
-    // The volume and the box: everything the host knows before a kernel.  No HIP call.
-    int resolve(const vr_label_request *req)
-    {
-        if (!c->bricks) return fail(c, VR_EINVAL, "no volume");
-        const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-        if (const char *m = label_box_resolve(req->use_box, req->box_min, req->box_max, dims, &box))
-            return fail(c, VR_EINVAL, m);
-        std::memset(&A, 0, sizeof A);
-        const uint32_t cells[3] = {(uint32_t)brick_cells(c->layout, 0), (uint32_t)brick_cells(c->layout, 1),
-                                   (uint32_t)brick_cells(c->layout, 2)};
-        const uint64_t nwork = label_brick_range(box, cells, (uint32_t)kPad, A.b0, A.nb);
-        if (nwork >= 1ull << 31) return fail(c, VR_EINVAL, "label box holds too many bricks");
-        for (int a = 0; a < 3; ++a) {
-            A.blo[a] = box.lo[a];
-            A.bhi[a] = box.hi[a];
-            A.ext[a] = box.ext[a];
-        }
-        A.lo = req->lo;
-        A.hi = req->hi;
-        A.nwork = (uint32_t)nwork;
-        A.nvox = (uint32_t)box.voxels;
-        A.nwords = (uint32_t)((box.voxels + 63) / 64);
-        A.nchunks = (uint32_t)((box.voxels + kLabelChunk - 1) / kLabelChunk);
-        A.nbx = bricks_for(c->nx, 0, c->layout);
-        A.nby = bricks_for(c->ny, 1, c->layout);
-        A.vol = c->bricks;
-        return VR_OK;
-    }
-    // The context's own label array, for the calls that hand no labels out on the device.
-    int own_labels()
-    {
-        HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-        return label_block(c, c->label_dev, c->label_bytes, (size_t)box.voxels * 4, "hipMalloc(labels)");
-    }
-    // The labelling passes into labels_dev, then the counts to the host (waits for s).  *I is
-    // written only on VR_OK: voxels, in_voxels and components.
-    int label(const vr_label_request *req, void *labels_dev, vr_label_info *I)
-    {
-        HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-        const LabelScratch sc = label_scratch(box.voxels);
-        if (int rc = label_block(c, c->label_aux_dev, c->label_aux_bytes, sc.bytes, "hipMalloc(label root table)"))
-            return rc;
-        char *base = static_cast<char *>(c->label_aux_dev);
-        A.P = static_cast<uint32_t *>(labels_dev);
-        A.mask = reinterpret_cast<unsigned long long *>(base + sc.mask);
-        A.wpre = reinterpret_cast<uint32_t *>(base + sc.wpre);
-        A.chunk = reinterpret_cast<uint32_t *>(base + sc.chunk);
-        A.out = reinterpret_cast<unsigned long long *>(base + sc.out);
-        HIP_TRY(c, hipMemsetAsync(A.out, 0, 32, s), "hipMemset(label counts)");
-        for (float &v : c->label_pass_ms) v = 0.0f;
-        if (int rc = begin()) return rc;
-        std::string name;
-        for (int pass = 0; pass < kLabelPasses; ++pass) {  // local, seam, flatten, scan
-            HIP_TRY(c, launch_label(c->layout, (int)req->connectivity, pass, A, s, &name), "label launch");
-            if (pass + 1 < kLabelPasses)
-                if (int rc = mark(kLabelLocal + pass)) return rc;
-        }
-        c->last_mpr_name = name;
-        if (int rc = end()) return rc;
-        unsigned long long h[2];
-        HIP_TRY(c, hipMemcpyAsync(h, A.out, sizeof h, hipMemcpyDeviceToHost, s), "hipMemcpy(label counts)");
-        HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize(label counts)");
-        if (int rc = passes_read(kLabelScan)) return rc;
-        std::memset(I, 0, sizeof *I);
-        I->voxels = box.voxels;
-        I->components = h[0];
-        I->in_voxels = h[1];
-        return VR_OK;
-    }
-    // The component table of I->components records into the context's block (A.comps), and the
-    // largest component into *I (waits for s).
-    int table(vr_label_info *I)
-    {
-        if (!I->components) return VR_OK;
-        if (int rc = label_block(c, c->label_tab_dev, c->label_tab_bytes,
-                                 (size_t)I->components * kLabelComponentBytes, "hipMalloc(label components)"))
-            return rc;
-        A.comps = c->label_tab_dev;
-        A.ncomps = (uint32_t)I->components;
-        if (int rc = begin()) return rc;
-        for (int pass = 0; pass < 3; ++pass) {  // init, accumulate, largest
-            HIP_TRY(c, launch_label_table(pass, A, s), "label table launch");
-            if (pass < 2)
-                if (int rc = mark(kLabelTableInit + pass)) return rc;
-        }
-        if (int rc = end()) return rc;
-        unsigned long long key = 0;
-        HIP_TRY(c, hipMemcpyAsync(&key, A.out + 2, sizeof key, hipMemcpyDeviceToHost, s), "hipMemcpy(label largest)");
-        HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize(label largest)");
-        if (int rc = passes_read(kLabelLargest)) return rc;
-        I->largest_voxels = key >> 32;
-        I->largest_label = ~(uint32_t)key;
-        return VR_OK;
-    }
-    // The seed's component: the mask into mask_dev and its record into *comp (waits for s).
-    int grow(const vr_label_request *req, const uint32_t seed[3], void *mask_dev, vr_label_component *comp)
-    {
-        if (int rc = own_labels()) return rc;
-        vr_label_info I;
-        if (int rc = label(req, c->label_dev, &I)) return rc;
-        uint32_t lab = 0;
-        HIP_TRY(c, hipMemcpyAsync(&lab, A.P + (size_t)label_linear(box, seed), sizeof lab, hipMemcpyDeviceToHost, s),
-                "hipMemcpy(seed label)");
-        HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize(seed label)");
-        vr_label_component R;
-        std::memset(&R, 0, sizeof R);
-        if (!lab) {
-            HIP_TRY(c, hipMemsetAsync(mask_dev, 0, (size_t)box.voxels, s), "hipMemset(region mask)");
-        } else {
-            if (int rc = label_block(c, c->label_tab_dev, c->label_tab_bytes, kLabelComponentBytes,
-                                     "hipMalloc(label components)"))
-                return rc;
-            A.comps = c->label_tab_dev;
-            A.ncomps = 1;
-            A.grow = static_cast<uint8_t *>(mask_dev);
-            A.seed_label = lab;
-            if (int rc = begin()) return rc;
-            HIP_TRY(c, launch_label_table(0, A, s), "label table launch");
-            if (int rc = mark(kLabelTableInit)) return rc;
-            HIP_TRY(c, launch_label_grow(A, s), "region grow launch");
-            if (int rc = end()) return rc;
-            HIP_TRY(c, hipMemcpyAsync(&R, A.comps, sizeof R, hipMemcpyDeviceToHost, s), "hipMemcpy(region record)");
-        }
-        HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize(region grow)");
-        if (lab)
-            if (int rc = passes_read(kLabelGrow)) return rc;
-        R.label = lab;
-        *comp = R;
-        return VR_OK;
-    }
-};
-static_assert(sizeof(vr_label_component) == kLabelComponentBytes && sizeof(vr_label_info) == 40 &&
-                  sizeof(vr_label_request) == 40,
-              "vr_label.h");
-
-// info for the capacity refusal that is known on the host: the voxels of N alone
-void label_info_voxels(vr_label_info *info, uint64_t voxels)
-{
-    std::memset(info, 0, sizeof *info);
-    info->voxels = voxels;
-}
-}  // namespace
-
-extern "C" {
-
-int vr_label_count(vr_ctx *c, const vr_label_request *req, vr_label_info *info)
-{
-    if (int rc = check_label_request(c, req, info, info, info)) return rc;
-    if (is_group(c)) {  // on the lowest device, which holds a replica
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_label_count(c->members[0], req, info));
-    }
-    LabelRun R{c, nullptr};
-    if (int rc = R.resolve(req)) return rc;
-    if (int rc = R.own_labels()) return rc;
-    vr_label_info I;
-    if (int rc = R.label(req, c->label_dev, &I)) return rc;
-    if (int rc = R.table(&I)) return rc;
-    *info = I;
-    return VR_OK;
-}
-
-int vr_label_components_device(vr_ctx *c, const vr_label_request *req, void *labels_dev, uint64_t lcap,
-                               void *comps_dev, uint64_t ccap, vr_label_info *info, void *stream)
-{
-    if (int rc = check_label_request(c, req, labels_dev, comps_dev, info)) return rc;
-    if (!label_pointer_ok(labels_dev)) return fail(c, VR_EINVAL, "labels_dev must be 4-byte aligned");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_label_components_device(c->members[0], req, labels_dev, lcap, comps_dev, ccap, info,
-                                                    stream));
-    }
-    LabelRun R{c, static_cast<hipStream_t>(stream)};
-    if (int rc = R.resolve(req)) return rc;
-    if (!label_capacity_ok(lcap, R.box.voxels)) {
-        label_info_voxels(info, R.box.voxels);
-        return fail(c, VR_ENOSPC, "label buffer is smaller than the box (see the info's voxels)");
-    }
-    vr_label_info I;
-    if (int rc = R.label(req, labels_dev, &I)) return rc;
-    if (int rc = R.table(&I)) return rc;
-    if (!label_capacity_ok(ccap, I.components)) {
-        *info = I;
-        return fail(c, VR_ENOSPC, "component buffer is smaller than the table (see the info's components)");
-    }
-    if (I.components) {
-        HIP_TRY(c, hipMemcpyAsync(comps_dev, R.A.comps, (size_t)I.components * kLabelComponentBytes,
-                                  hipMemcpyDeviceToDevice, R.s), "hipMemcpy(label components)");
-        HIP_TRY(c, hipStreamSynchronize(R.s), "hipStreamSynchronize(label components)");
-    }
-    *info = I;
-    return VR_OK;
-}
-
-int vr_label_components(vr_ctx *c, const vr_label_request *req, uint32_t *labels_host, uint64_t lcap,
-                        vr_label_component *comps_host, uint64_t ccap, vr_label_info *info)
-{
-    if (int rc = check_label_request(c, req, labels_host, comps_host, info)) return rc;
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_label_components(c->members[0], req, labels_host, lcap, comps_host, ccap, info));
-    }
-    LabelRun R{c, nullptr};
-    if (int rc = R.resolve(req)) return rc;
-    if (!label_capacity_ok(lcap, R.box.voxels)) {
-        label_info_voxels(info, R.box.voxels);
-        return fail(c, VR_ENOSPC, "label buffer is smaller than the box (see the info's voxels)");
-    }
-    if (int rc = R.own_labels()) return rc;
-    vr_label_info I;
-    if (int rc = R.label(req, c->label_dev, &I)) return rc;
-    if (int rc = R.table(&I)) return rc;
-    HIP_TRY(c, hipMemcpy(labels_host, c->label_dev, (size_t)R.box.voxels * 4, hipMemcpyDeviceToHost),
-            "hipMemcpy(labels)");
-    if (!label_capacity_ok(ccap, I.components)) {
-        *info = I;
-        return fail(c, VR_ENOSPC, "component buffer is smaller than the table (see the info's components)");
-    }
-    if (I.components)
-        HIP_TRY(c, hipMemcpy(comps_host, R.A.comps, (size_t)I.components * kLabelComponentBytes,
-                             hipMemcpyDeviceToHost), "hipMemcpy(label components)");
-    *info = I;
-    return VR_OK;
-}
-
-int vr_region_grow_device(vr_ctx *c, const vr_label_request *req, const uint32_t seed[3], void *mask_dev,
-                          uint64_t mcap, vr_label_component *comp_out, void *stream)
-{
-    if (int rc = check_label_request(c, req, seed, mask_dev, comp_out)) return rc;
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_region_grow_device(c->members[0], req, seed, mask_dev, mcap, comp_out, stream));
-    }
-    LabelRun R{c, static_cast<hipStream_t>(stream)};
-    if (int rc = R.resolve(req)) return rc;
-    if (!label_seed_ok(R.box, seed)) return fail(c, VR_EINVAL, "seed lies outside the box");
-    if (!label_capacity_ok(mcap, R.box.voxels))
-        return fail(c, VR_ENOSPC, "mask buffer is smaller than the box");
-    return R.grow(req, seed, mask_dev, comp_out);
-}
-
-int vr_region_grow(vr_ctx *c, const vr_label_request *req, const uint32_t seed[3], uint8_t *mask_host,
-                   uint64_t mcap, vr_label_component *comp_out)
-{
-    if (int rc = check_label_request(c, req, seed, mask_host, comp_out)) return rc;
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_region_grow(c->members[0], req, seed, mask_host, mcap, comp_out));
-    }
-    LabelRun R{c, nullptr};
-    if (int rc = R.resolve(req)) return rc;
-    if (!label_seed_ok(R.box, seed)) return fail(c, VR_EINVAL, "seed lies outside the box");
-    if (!label_capacity_ok(mcap, R.box.voxels))
-        return fail(c, VR_ENOSPC, "mask buffer is smaller than the box");
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    if (int rc = label_block(c, c->label_out_dev, c->label_out_bytes, (size_t)R.box.voxels, "hipMalloc(region mask)"))
-        return rc;
-    vr_label_component comp;
-    if (int rc = R.grow(req, seed, c->label_out_dev, &comp)) return rc;
-    HIP_TRY(c, hipMemcpy(mask_host, c->label_out_dev, (size_t)R.box.voxels, hipMemcpyDeviceToHost),
-            "hipMemcpy(region mask)");
-    *comp_out = comp;
-    return VR_OK;
-}
-
-}  // extern "C"
-
-// ---- isosurface mesh (include/vr/vr_mesh.h) --------------------------------------------------
-namespace {
-// What vr_mesh.h refuses before it looks at the context: the NULL arguments and the request's own
-// fields (csrc/vr_mesh_host.h); no HIP call.
-int check_mesh_request(vr_ctx *c, const vr_mesh_request *req, const void *info)
-{
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
-    if (!req || !info) return fail(c, VR_EINVAL, "NULL argument");
-    if (const char *m = mesh_flags_error(req->iso, req->closed, req->normals, req->use_box))
-        return fail(c, VR_EINVAL, m);
-    return VR_OK;
-}
-
-// One call's passes on stream s; c is a single-device context.  The timing events bracket the
-// classify pass with its scans as one interval and the two emit passes as another (the copy of
-// the counts to the host and the host's wait for it lie between the two).
-struct MeshRun {
-    vr_ctx *c;
-    hipStream_t s;
-    MeshArgs A;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-
-    int begin()
-    {
-        if (!c->timing) return VR_OK;
-        e0 = pooled_event(c);
-        e1 = pooled_event(c);
-        if (!e0 || !e1) return fail(c, VR_EIO, "hipEventCreate failed");
-        HIP_TRY(c, hipEventRecord(e0, s), "hipEventRecord");
-        return VR_OK;
-    }
-    int end()
-    {
-        if (e0 && e1) {
-            HIP_TRY(c, hipEventRecord(e1, s), "hipEventRecord");
-            c->ev_pending.emplace_back(e0, e1);
-        }
-        e0 = e1 = nullptr;
-        return VR_OK;
-    }
-
-    // The classify pass and the scans, then the counts to the host (waits for s).  *I is written
-    // only on VR_OK.
-    int count(const vr_mesh_request *req, vr_mesh_info *I)
-    {
-        if (!c->bricks) return fail(c, VR_EINVAL, "no volume");
-        const uint32_t dims[3] = {c->nx, c->ny, c->nz};
-        MeshBox box;
-        if (const char *m = mesh_box_resolve(req->use_box, req->box_min, req->box_max, req->closed, dims, &box))
-            return fail(c, VR_EINVAL, m);
-        std::memset(&A, 0, sizeof A);
-        const uint32_t cells[3] = {(uint32_t)brick_cells(c->layout, 0), (uint32_t)brick_cells(c->layout, 1),
-                                   (uint32_t)brick_cells(c->layout, 2)};
-        const uint64_t nwork = mesh_brick_range(box, cells, (uint32_t)kPad, A.b0, A.nb);
-        if (nwork >= 1ull << 31) return fail(c, VR_EINVAL, "mesh box holds too many bricks");
-        for (int a = 0; a < 3; ++a) {
-            A.dims[a] = dims[a];
-            A.fdims[a] = (float)dims[a];
-            A.lo[a] = box.lo[a];
-            A.hi[a] = box.hi[a];
-            A.clo[a] = (int32_t)box.clo[a];
-            A.chi[a] = (int32_t)box.chi[a];
-        }
-        A.iso = req->iso;
-        A.nwork = (uint32_t)nwork;
-        A.nchunks = (A.nwork + kMeshChunk - 1) / kMeshChunk;
-        A.nbx = bricks_for(c->nx, 0, c->layout);
-        A.nby = bricks_for(c->ny, 1, c->layout);
-        A.vol = c->bricks;
-        HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-        const MeshScratch sc = mesh_scratch(nwork);
-        if (c->mesh_bytes < sc.bytes) {
-            // (an earlier call's passes may still read the old block on another stream)
-            HIP_TRY(c, hipDeviceSynchronize(), "hipDeviceSynchronize (mesh scratch)");
-            if (c->mesh_dev) hipFree(c->mesh_dev);
-            c->mesh_dev = nullptr;
-            c->mesh_bytes = 0;
-            HIP_TRY(c, hipMalloc(&c->mesh_dev, sc.bytes), "hipMalloc(mesh scratch)");
-            c->mesh_bytes = sc.bytes;
-        }
-        char *base = static_cast<char *>(c->mesh_dev);
-        A.mask = reinterpret_cast<uint32_t *>(base + sc.mask);
-        A.cnt = reinterpret_cast<uint2 *>(base + sc.cnt);
-        A.pre = reinterpret_cast<uint2 *>(base + sc.pre);
-        A.chunk = reinterpret_cast<unsigned long long *>(base + sc.chunk);
-        A.out = reinterpret_cast<unsigned long long *>(base + sc.out);
-        HIP_TRY(c, hipMemsetAsync(A.out, 0, 32, s), "hipMemset(mesh counts)");
-        if (int rc = begin()) return rc;
-        std::string name;
-        HIP_TRY(c, launch_mesh_classify(c->layout, A, s, &name), "mesh classify launch");
-        c->last_mpr_name = name;
-        if (int rc = end()) return rc;
-        unsigned long long h[3];
-        HIP_TRY(c, hipMemcpyAsync(h, A.out, sizeof h, hipMemcpyDeviceToHost, s), "hipMemcpy(mesh counts)");
-        HIP_TRY(c, hipStreamSynchronize(s), "hipStreamSynchronize(mesh counts)");
-        if (h[0] > kMeshMaxVertices) return fail(c, VR_EINVAL, "mesh has more than 2^32 - 1 vertices");
-        std::memset(I, 0, sizeof *I);
-        I->vertices = h[0];
-        I->triangles = 2 * h[1];
-        I->inside_voxels = h[2];
-        return VR_OK;
-    }
-    // The two emit passes into device buffers that hold I's counts.
-    int emit(const vr_mesh_request *req, const vr_mesh_info &I, void *verts_dev, void *tris_dev)
-    {
-        A.verts = verts_dev;
-        A.tris = static_cast<uint32_t *>(tris_dev);
-        if (!I.vertices) return VR_OK;  // (no vertex, no triangle)
-        if (int rc = begin()) return rc;
-        HIP_TRY(c, launch_mesh_vertices(c->layout, req->normals != 0, A, s), "mesh vertex launch");
-        if (I.triangles) HIP_TRY(c, launch_mesh_quads(c->layout, A, s), "mesh quad launch");
-        return end();
-    }
-};
-}  // namespace
-
-extern "C" {
-
-int vr_mesh_count(vr_ctx *c, const vr_mesh_request *req, vr_mesh_info *info)
-{
-    if (int rc = check_mesh_request(c, req, info)) return rc;
-    if (is_group(c)) {  // on the lowest device, which holds a replica
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0], vr_mesh_count(c->members[0], req, info));
-    }
-    MeshRun R{c, nullptr};
-    vr_mesh_info I;
-    if (int rc = R.count(req, &I)) return rc;
-    *info = I;
-    return VR_OK;
-}
-
-int vr_mesh_extract_device(vr_ctx *c, const vr_mesh_request *req, void *verts_dev, uint64_t vcap,
-                           void *tris_dev, uint64_t tcap, vr_mesh_info *info, void *stream)
-{
-    if (int rc = check_mesh_request(c, req, info)) return rc;
-    if (!verts_dev || !tris_dev) return fail(c, VR_EINVAL, "NULL argument");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_mesh_extract_device(c->members[0], req, verts_dev, vcap, tris_dev, tcap, info, stream));
-    }
-    MeshRun R{c, static_cast<hipStream_t>(stream)};
-    vr_mesh_info I;
-    if (int rc = R.count(req, &I)) return rc;
-    if (I.vertices > vcap || I.triangles > tcap) {
-        *info = I;
-        return fail(c, VR_ENOSPC, "mesh buffers are smaller than the mesh (see the info's counts)");
-    }
-    if (int rc = R.emit(req, I, verts_dev, tris_dev)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(R.s), "hipStreamSynchronize(mesh)");
-    *info = I;
-    return VR_OK;
-}
-
-int vr_mesh_extract(vr_ctx *c, const vr_mesh_request *req, vr_mesh_vertex *verts_host, uint64_t vcap,
-                    uint32_t *tris_host, uint64_t tcap, vr_mesh_info *info)
-{
-    if (int rc = check_mesh_request(c, req, info)) return rc;
-    if (!verts_host || !tris_host) return fail(c, VR_EINVAL, "NULL argument");
-    if (is_group(c)) {
-        if (int rc = group_idle(c)) return rc;
-        return member_rc(c, c->members[0],
-                         vr_mesh_extract(c->members[0], req, verts_host, vcap, tris_host, tcap, info));
-    }
-    MeshRun R{c, nullptr};
-    vr_mesh_info I;
-    if (int rc = R.count(req, &I)) return rc;
-    if (I.vertices > vcap || I.triangles > tcap) {
-        *info = I;
-        return fail(c, VR_ENOSPC, "mesh buffers are smaller than the mesh (see the info's counts)");
-    }
-    // vertices, then (16-aligned) triangles, in the context's own device block
-    const size_t vbytes = (size_t)I.vertices * kMeshVertexBytes, tbytes = (size_t)I.triangles * kMeshTriangleBytes;
-    const size_t toff = (vbytes + 15) & ~(size_t)15, bytes = toff + tbytes;
-    if (c->mesh_out_bytes < bytes) {
-        if (c->mesh_out_dev) hipFree(c->mesh_out_dev);  // (its last mesh was copied out synchronously)
-        c->mesh_out_dev = nullptr;
-        c->mesh_out_bytes = 0;
-        HIP_TRY(c, hipMalloc(&c->mesh_out_dev, bytes), "hipMalloc(mesh)");
-        c->mesh_out_bytes = bytes;
-    }
-    char *dev = static_cast<char *>(c->mesh_out_dev);
-    if (int rc = R.emit(req, I, dev, dev + toff)) return rc;
-    if (vbytes) HIP_TRY(c, hipMemcpy(verts_host, dev, vbytes, hipMemcpyDeviceToHost), "hipMemcpy(mesh vertices)");
-    if (tbytes) HIP_TRY(c, hipMemcpy(tris_host, dev + toff, tbytes, hipMemcpyDeviceToHost), "hipMemcpy(mesh triangles)");
-    HIP_TRY(c, hipDeviceSynchronize(), "hipDeviceSynchronize(mesh)");
-    *info = I;
     return VR_OK;
 }
 

@@ -1,12 +1,14 @@
 // vr_hist_host.h — the host side of include/vr/vr_hist.h: the bin edges, the bin of a value and
 // the percentile window.  Plain C++ without HIP, so a stand-alone program can run it (under a
-// sanitizer, tests/test_hist_cpu.py); vr_api.hip includes it for vr_hist_edges, vr_hist_window
+// sanitizer, tests/test_hist_cpu.py); vr_api_hist.hip includes it for vr_hist_edges, vr_hist_window
 // and the edge table hist_kernel corrects its first guess against.
 #pragma once
 
 #include <stdint.h>
 
 #include <cmath>
+
+#include "vr_box_host.h"  // the request box: the shared rule as it is
 
 namespace vr {
 

@@ -1,6 +1,6 @@
 // vr_hit_host.h — the host side of include/vr/vr_hit.h: what a hit request is refused for, and
 // the pixel rectangle it resolves to on a W x H framebuffer.  Plain C++ without HIP, so a
-// stand-alone program can run it (under a sanitizer, tests/test_hit_cpu.py); vr_api.hip includes
+// stand-alone program can run it (under a sanitizer, tests/test_hit_cpu.py); vr_api_hit.hip includes
 // it for vr_hit_render, vr_hit_render_device, vr_hit_count_work and vr_pick.
 #pragma once
 

@@ -1,24 +1,22 @@
 // vr_label_host.h — the host side of include/vr/vr_label.h: what a label request is refused for,
 // the voxel box it resolves to on an nx x ny x nz volume, the 2^32 - 1 bound, the seed and capacity
-// checks, and the bricks a launch walks.  Plain C++ without HIP, so a stand-alone program can run
-// it (under a sanitizer, tests/test_label_cpu.py); vr_api.hip includes it for vr_label_* and
-// vr_region_grow*.
+// checks (the bricks a launch walks: vr_box_host.h).  Plain C++ without HIP, so a stand-alone program
+// can run it (under a sanitizer, tests/test_label_cpu.py); vr_api_label.hip includes it for
+// vr_label_* and vr_region_grow*.
 #pragma once
 
 #include <stdint.h>
 
 #include <cmath>
 
+#include "vr_box_host.h"
+
 namespace vr {
 
 constexpr uint32_t kLabelComponentBytes = 64;          // sizeof(vr_label_component)
 constexpr uint64_t kLabelMaxVoxels = 0xFFFFFFFFull;    // a label is 1 + a box-linear index, in 32 bits
 
-// The voxel box [lo, hi) of a request, its extents and its voxel count.
-struct LabelBox {
-    uint32_t lo[3], hi[3], ext[3];
-    uint64_t voxels;
-};
+using LabelBox = VoxelBox;  // (vr_box_host.h)
 
 // nullptr: lo, hi, connectivity and use_box are what vr_label.h allows; else what is wrong.
 inline const char *label_request_error(float lo, float hi, uint32_t connectivity, uint32_t use_box)
@@ -31,25 +29,17 @@ inline const char *label_request_error(float lo, float hi, uint32_t connectivity
 }
 
 // The box of a request on a volume of dims voxels into *b; nullptr, or what is wrong (*b is then
-// untouched).  The histogram's rule: box_min < box_max <= dims per axis; and at most 2^32 - 1
-// voxels, so that every label fits.
+// untouched).  The shared rule (box_resolve), and at most 2^32 - 1 voxels, so that every label fits.
 inline const char *label_box_resolve(uint32_t use_box, const uint32_t box_min[3], const uint32_t box_max[3],
                                      const uint32_t dims[3], LabelBox *b)
 {
-    if (use_box > 1) return "label use_box must be 0 or 1";
     LabelBox r;
-    r.voxels = 1;
-    bool over = false;
-    for (int a = 0; a < 3; ++a) {
-        r.lo[a] = use_box ? box_min[a] : 0u;
-        r.hi[a] = use_box ? box_max[a] : dims[a];
-        if (r.lo[a] >= r.hi[a] || r.hi[a] > dims[a]) return "label box is empty or beyond the volume";
-        r.ext[a] = r.hi[a] - r.lo[a];
-        // (three factors below 2^32: the product may pass 64 bits)
-        if (r.voxels > kLabelMaxVoxels / r.ext[a]) over = true;
-        if (!over) r.voxels *= r.ext[a];
+    switch (box_resolve(use_box, box_min, box_max, dims, &r)) {
+        case kBoxUse: return "label use_box must be 0 or 1";
+        case kBoxEmpty: return "label box is empty or beyond the volume";
+        case kBoxOk: break;
     }
-    if (over || r.voxels > kLabelMaxVoxels) return "label box holds more than 2^32 - 1 voxels: label it box by box";
+    if (r.voxels > kLabelMaxVoxels) return "label box holds more than 2^32 - 1 voxels: label it box by box";
     *b = r;
     return nullptr;
 }
@@ -74,20 +64,5 @@ inline bool label_pointer_ok(const void *labels) { return (reinterpret_cast<uint
 
 // A buffer of cap records holds the n of a result.
 inline bool label_capacity_ok(uint64_t cap, uint64_t n) { return cap >= n; }
-
-// The bricks that hold the box's voxels (padded indices lo + pad .. hi - 1 + pad): first and count
-// per axis; returns their product (never 0; UINT64_MAX where it passes 64 bits).
-inline uint64_t label_brick_range(const LabelBox &b, const uint32_t cells[3], uint32_t pad, uint32_t b0[3],
-                                  uint32_t nb[3])
-{
-    uint64_t n = 1;
-    for (int a = 0; a < 3; ++a) {
-        const uint64_t first = (uint64_t)b.lo[a] + pad, last = (uint64_t)b.hi[a] - 1 + pad;
-        b0[a] = (uint32_t)(first / cells[a]);
-        nb[a] = (uint32_t)(last / cells[a]) - b0[a] + 1;
-        n = n > UINT64_MAX / nb[a] ? UINT64_MAX : n * nb[a];
-    }
-    return n;
-}
 
 }  // namespace vr

@@ -1,7 +1,7 @@
 // vr_mesh_host.h — the host side of include/vr/vr_mesh.h: what a mesh request is refused for, the
 // node box and the cell range it resolves to on an nx x ny x nz volume, and the bricks a launch
 // walks.  Plain C++ without HIP, so a stand-alone program can run it (under a sanitizer,
-// tests/test_mesh_cpu.py); vr_api.hip includes it for vr_mesh_count, vr_mesh_extract and
+// tests/test_mesh_cpu.py); vr_api_mesh.hip includes it for vr_mesh_count, vr_mesh_extract and
 // vr_mesh_extract_device.
 #pragma once
 
@@ -10,6 +10,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+
+#include "vr_box_host.h"
 
 namespace vr {
 
@@ -20,8 +22,7 @@ constexpr uint64_t kMeshMaxVertices = 0xFFFFFFFFull;  // an index is a uint32_t
 // The node box [lo, hi) of a request and its cell range [clo, chi] (both ends included; logical
 // cell indices, -1 allowed: the closed mesh's ring cell below voxel 0).  An axis of one node and
 // closed = 0 has no cell: chi < clo there.
-struct MeshBox {
-    uint32_t lo[3], hi[3];
+struct MeshBox : VoxelBox {
     int64_t clo[3], chi[3];
 };
 
@@ -36,17 +37,15 @@ inline const char *mesh_flags_error(float iso, uint32_t closed, uint32_t normals
 }
 
 // The box of a request on a volume of dims voxels into *b; nullptr, or what is wrong (*b is then
-// untouched).  The histogram's rule: box_min < box_max <= dims per axis.
+// untouched).  The shared rule (box_resolve).
 inline const char *mesh_box_resolve(uint32_t use_box, const uint32_t box_min[3], const uint32_t box_max[3],
                                     uint32_t closed, const uint32_t dims[3], MeshBox *b)
 {
     if (use_box > 1) return "mesh use_box must be 0 or 1";
     if (closed > 1) return "mesh closed must be 0 or 1";
     MeshBox r;
+    if (box_resolve(use_box, box_min, box_max, dims, &r)) return "mesh box is empty or beyond the volume";
     for (int a = 0; a < 3; ++a) {
-        r.lo[a] = use_box ? box_min[a] : 0u;
-        r.hi[a] = use_box ? box_max[a] : dims[a];
-        if (r.lo[a] >= r.hi[a] || r.hi[a] > dims[a]) return "mesh box is empty or beyond the volume";
         r.clo[a] = closed ? (int64_t)r.lo[a] - 1 : (int64_t)r.lo[a];
         r.chi[a] = closed ? (int64_t)r.hi[a] - 1 : (int64_t)r.hi[a] - 2;
     }
@@ -56,19 +55,12 @@ inline const char *mesh_box_resolve(uint32_t use_box, const uint32_t box_min[3],
 
 // The bricks a launch walks: those that hold the padded cells [clo + pad, hi - 1 + pad] per axis
 // -- the cell set's, and in an open mesh also the cell of the box's last voxel, which is in no
-// cell of the set but counts for inside_voxels.  cells[a]: the brick's cells along a.  first and
-// count per axis; returns their product (never 0; UINT64_MAX where it passes 64 bits).
+// cell of the set but counts for inside_voxels (box_brick_range with clo as the first index).
 inline uint64_t mesh_brick_range(const MeshBox &b, const uint32_t cells[3], uint32_t pad, uint32_t b0[3],
                                  uint32_t nb[3])
 {
-    uint64_t n = 1;
-    for (int a = 0; a < 3; ++a) {
-        const uint64_t first = (uint64_t)(b.clo[a] + (int64_t)pad), last = (uint64_t)b.hi[a] - 1 + pad;
-        b0[a] = (uint32_t)(first / cells[a]);
-        nb[a] = (uint32_t)(last / cells[a]) - b0[a] + 1;
-        n = n > UINT64_MAX / nb[a] ? UINT64_MAX : n * nb[a];  // (saturates: the caller bounds it)
-    }
-    return n;
+    const int64_t last[3] = {b.hi[0] - 1ll, b.hi[1] - 1ll, b.hi[2] - 1ll};
+    return box_brick_range(b.clo, last, cells, pad, b0, nb);
 }
 
 // vr_host.h vr_mesh_write_ply: a binary little-endian PLY of nv vertex records (24 bytes: pos[3],
