@@ -136,6 +136,8 @@ def straddling(labels, origin=(0, 0, 0), cells=(8, 8, 8), pad=2):
     padded index = volume index + pad)."""
     lab = labels.reshape(-1)
     sel = np.flatnonzero(lab)
+    if not sel.size:  # no component: reduceat refuses an empty array
+        return 0
     nz, ny, nx = labels.shape
     bx = (sel % nx + origin[0] + pad) // cells[0]
     by = ((sel // nx) % ny + origin[1] + pad) // cells[1]
