@@ -160,6 +160,12 @@ struct vr_ctx {
     // box), the root table (vr_internal.h LabelScratch), the component records and vr_region_grow's
     // device copy of the host mask; all grown on demand
     DevBlock label_dev, label_aux_dev, label_tab_dev, label_out_dev;
+    // vr_edt_squared*, vr_mask_morph* (vr_morph.h; csrc/vr_api_morph.hip in lib/libvr_amd_morph.so):
+    // the morphology's distance (4 bytes per voxel of the grid), the intermediate mask of open and
+    // close (1 byte per voxel), the counters, and the host forms' device copies of their arrays; all
+    // grown on demand.  morph_last_name: the family's last kernel (vr_morph_last_kernel_name)
+    DevBlock morph_dist_dev, morph_tmp_dev, morph_cnt_dev, morph_io_dev;
+    const char *morph_last_name = "";
     // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
     // taken while timing is enabled; 0 for a pass that call did not run
     float label_pass_ms[kLabelPassSlots] = {};

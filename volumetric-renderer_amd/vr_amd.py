@@ -146,6 +146,15 @@ class vr_label_info(C.Structure):  # vr_label.h
                 ("largest_voxels", C.c_uint64), ("largest_label", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class vr_edt_info(C.Structure):  # vr_morph.h
+    _fields_ = [("voxels", C.c_uint64), ("target_voxels", C.c_uint64), ("max_dist2", C.c_uint32),
+                ("max_index", C.c_uint32)]
+
+
+class vr_morph_info(C.Structure):  # vr_morph.h
+    _fields_ = [("voxels", C.c_uint64), ("in_set", C.c_uint64), ("out_set", C.c_uint64)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -214,6 +223,14 @@ LABEL_SYMBOLS = ["vr_label_count", "vr_label_components", "vr_label_components_d
                  "vr_region_grow", "vr_region_grow_device"]
 LABEL_COMPONENT_DTYPE = np.dtype([("label", "<u4"), ("reserved", "<u4"), ("voxels", "<u8"),
                                   ("bbox_min", "<u4", 3), ("bbox_max", "<u4", 3), ("sum", "<u8", 3)])
+# include/vr/vr_morph.h: the exact distance transform of a mask and ball morphology; the entry points
+# live in a second library, lib/libvr_amd_morph.so (morph_lib()), on the same context
+MORPH_SYMBOLS = ["vr_edt_squared", "vr_edt_squared_device", "vr_mask_morph", "vr_mask_morph_device",
+                 "vr_morph_last_kernel_name"]
+EDT_NONE = 0xFFFFFFFF
+EDT_TO_SET, EDT_TO_UNSET = 0, 1
+MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
+MORPH_MAX_EXTENT = 32768
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -379,6 +396,39 @@ def lib() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} has ABI {L.vr_abi_version()}, this binding expects "
                            f"{ABI_VERSION}: rebuild it")
     _LIB = L
+    return L
+
+
+MORPH_LIB_PATH = os.environ.get("VR_AMD_MORPH_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                    "libvr_amd_morph.so")
+_MORPH_LIB = None
+
+
+def morph_lib() -> C.CDLL:
+    """Load lib/libvr_amd_morph.so (vr_morph.h) on first use, after lib(): it takes the host
+    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
+    global _MORPH_LIB
+    if _MORPH_LIB is not None:
+        return _MORPH_LIB
+    lib()
+    if not os.path.exists(MORPH_LIB_PATH):
+        raise RuntimeError(f"{MORPH_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
+                           "(or __graft_entry__.build()); there is no CPU fallback")
+    L = C.CDLL(MORPH_LIB_PATH)
+    vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+    ext = C.POINTER(u32)
+    sig = {
+        "vr_edt_squared_device": (i32, [vp, ext, vp, u32, u32, vp, u64, C.POINTER(vr_edt_info), vp]),
+        "vr_edt_squared": (i32, [vp, ext, vp, u32, u32, vp, u64, C.POINTER(vr_edt_info)]),
+        "vr_mask_morph_device": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, C.POINTER(vr_morph_info), vp]),
+        "vr_mask_morph": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, C.POINTER(vr_morph_info)]),
+        "vr_morph_last_kernel_name": (C.c_char_p, [vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _MORPH_LIB = L
     return L
 
 
@@ -1007,6 +1057,70 @@ class OffscreenPass:
         self._check(lib().vr_region_grow_device(self._ctx, C.byref(req), sd, C.c_void_p(mask_ptr), int(mcap),
                                                 C.byref(comp), C.c_void_p(stream or None)), "region_grow_device")
         return label_component_dict(comp)
+
+    # -- distance transform and ball morphology (vr_morph.h, lib/libvr_amd_morph.so) --
+    @staticmethod
+    def _edt_info(info: vr_edt_info) -> dict:
+        return {"voxels": info.voxels, "target_voxels": info.target_voxels, "max_dist2": info.max_dist2,
+                "max_index": info.max_index}
+
+    @staticmethod
+    def _morph_info(info: vr_morph_info) -> dict:
+        return {"voxels": info.voxels, "in_set": info.in_set, "out_set": info.out_set}
+
+    @staticmethod
+    def _morph_mask(mask):
+        """A (bz, by, bx) uint8 or uint32 array -> (the contiguous array, ext, elem_bytes)."""
+        m = np.ascontiguousarray(mask)
+        if m.ndim != 3 or m.dtype not in (np.dtype(np.uint8), np.dtype(np.uint32)):
+            raise ValueError("a mask is a (bz, by, bx) array of uint8 or uint32")
+        return m, (C.c_uint32 * 3)(m.shape[2], m.shape[1], m.shape[0]), m.dtype.itemsize
+
+    def distance_transform(self, mask, to_set=True) -> dict:
+        """vr_edt_squared: {"dist2": (bz, by, bx) uint32, "info": dict} -- the exact squared distance
+        of every voxel to the nearest set voxel of `mask` (to_set) or the nearest unset one."""
+        m, ext, eb = self._morph_mask(mask)
+        out = np.zeros(max(m.size, 1), np.uint32)  # (never a NULL buffer)
+        info = vr_edt_info()
+        self._check(morph_lib().vr_edt_squared(self._ctx, ext, m.ctypes.data, eb,
+                                               EDT_TO_SET if to_set else EDT_TO_UNSET, out.ctypes.data, m.size,
+                                               C.byref(info)), "distance_transform")
+        return {"dist2": out[:m.size].reshape(m.shape), "info": self._edt_info(info)}
+
+    def distance_transform_device(self, ext, mask_ptr: int, elem_bytes: int, dist2_ptr: int, dcap: int,
+                                  to_set=True, stream: int = 0) -> dict:
+        """vr_edt_squared_device: dcap distances into device memory on `stream`; returns the info
+        dict when the buffer is complete.  ext: (bx, by, bz)."""
+        info = vr_edt_info()
+        self._check(morph_lib().vr_edt_squared_device(
+            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.c_void_p(mask_ptr), int(elem_bytes),
+            EDT_TO_SET if to_set else EDT_TO_UNSET, C.c_void_p(dist2_ptr), int(dcap), C.byref(info),
+            C.c_void_p(stream or None)), "distance_transform_device")
+        return self._edt_info(info)
+
+    def morph(self, mask, op: int, r2: int) -> dict:
+        """vr_mask_morph: {"mask": (bz, by, bx) uint8 of 0/1, "info": dict} -- MORPH_DILATE, _ERODE,
+        _OPEN or _CLOSE of `mask` with the ball of squared radius r2."""
+        m, ext, eb = self._morph_mask(mask)
+        out = np.zeros(max(m.size, 1), np.uint8)  # (never a NULL buffer)
+        info = vr_morph_info()
+        self._check(morph_lib().vr_mask_morph(self._ctx, ext, int(op), int(r2), m.ctypes.data, eb,
+                                              out.ctypes.data, m.size, C.byref(info)), "morph")
+        return {"mask": out[:m.size].reshape(m.shape), "info": self._morph_info(info)}
+
+    def morph_device(self, ext, op: int, r2: int, mask_ptr: int, elem_bytes: int, out_ptr: int, mcap: int,
+                     stream: int = 0) -> dict:
+        """vr_mask_morph_device: mcap mask bytes into device memory on `stream`; returns the info
+        dict when the buffer is complete.  ext: (bx, by, bz)."""
+        info = vr_morph_info()
+        self._check(morph_lib().vr_mask_morph_device(
+            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), int(op), int(r2), C.c_void_p(mask_ptr),
+            int(elem_bytes), C.c_void_p(out_ptr), int(mcap), C.byref(info), C.c_void_p(stream or None)),
+            "morph_device")
+        return self._morph_info(info)
+
+    def morph_last_kernel_name(self) -> str:
+        return morph_lib().vr_morph_last_kernel_name(self._ctx).decode()
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
