@@ -166,6 +166,15 @@ struct vr_ctx {
     // grown on demand.  morph_last_name: the family's last kernel (vr_morph_last_kernel_name)
     DevBlock morph_dist_dev, morph_tmp_dev, morph_cnt_dev, morph_io_dev;
     const char *morph_last_name = "";
+    // vr_mask_label*, vr_mask_select* (vr_maskcc.h; csrc/vr_api_maskcc.hip in lib/libvr_amd_maskcc.so):
+    // vr_mask_select's labels (4 bytes per voxel of the grid), the root table and the counters, the
+    // records with their keep flags, and the host forms' device copies of their arrays; all grown on
+    // demand.  maskcc_last_name: the family's last kernel (vr_maskcc_last_kernel_name)
+    DevBlock maskcc_lab_dev, maskcc_aux_dev, maskcc_tab_dev, maskcc_io_dev;
+    const char *maskcc_last_name = "";
+    // kernel ms of the last call's passes (vr_maskcc_kernels.h MccPass), taken while timing is
+    // enabled; 0 for a pass that call did not run (vr_debug_maskcc_pass_ms, csrc/vr_api_maskcc.hip)
+    float maskcc_pass_ms[9] = {};
     // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
     // taken while timing is enabled; 0 for a pass that call did not run
     float label_pass_ms[kLabelPassSlots] = {};

@@ -155,6 +155,16 @@ class vr_morph_info(C.Structure):  # vr_morph.h
     _fields_ = [("voxels", C.c_uint64), ("in_set", C.c_uint64), ("out_set", C.c_uint64)]
 
 
+class vr_mask_select_request(C.Structure):  # vr_maskcc.h
+    _fields_ = [("rule", C.c_uint32), ("connectivity", C.c_uint32), ("min_voxels", C.c_uint64),
+                ("seed", C.c_uint32 * 3), ("reserved", C.c_uint32)]
+
+
+class vr_mask_select_info(C.Structure):  # vr_maskcc.h
+    _fields_ = [("voxels", C.c_uint64), ("in_set", C.c_uint64), ("out_set", C.c_uint64),
+                ("components", C.c_uint64), ("kept", C.c_uint64)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -231,6 +241,12 @@ EDT_NONE = 0xFFFFFFFF
 EDT_TO_SET, EDT_TO_UNSET = 0, 1
 MORPH_DILATE, MORPH_ERODE, MORPH_OPEN, MORPH_CLOSE = 0, 1, 2, 3
 MORPH_MAX_EXTENT = 32768
+# include/vr/vr_maskcc.h: the components of a mask -- labels, records, selection and hole filling; the
+# entry points live in a third library, lib/libvr_amd_maskcc.so (maskcc_lib()), on the same context
+MASKCC_SYMBOLS = ["vr_mask_label", "vr_mask_label_device", "vr_mask_select", "vr_mask_select_device",
+                  "vr_maskcc_last_kernel_name"]
+MASK_KEEP_LARGEST, MASK_KEEP_MIN_VOXELS, MASK_KEEP_SEED, MASK_FILL_HOLES = 0, 1, 2, 3
+MASKCC_MAX_EXTENT = 32768
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -430,6 +446,51 @@ def morph_lib() -> C.CDLL:
         fn.argtypes = args
     _MORPH_LIB = L
     return L
+
+
+MASKCC_LIB_PATH = os.environ.get("VR_AMD_MASKCC_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                      "libvr_amd_maskcc.so")
+_MASKCC_LIB = None
+
+
+def maskcc_lib() -> C.CDLL:
+    """Load lib/libvr_amd_maskcc.so (vr_maskcc.h) on first use, after lib(): it takes the host
+    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
+    global _MASKCC_LIB
+    if _MASKCC_LIB is not None:
+        return _MASKCC_LIB
+    lib()
+    if not os.path.exists(MASKCC_LIB_PATH):
+        raise RuntimeError(f"{MASKCC_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
+                           "(or __graft_entry__.build()); there is no CPU fallback")
+    L = C.CDLL(MASKCC_LIB_PATH)
+    vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
+    ext = C.POINTER(u32)
+    req, li, si = C.POINTER(vr_mask_select_request), C.POINTER(vr_label_info), C.POINTER(vr_mask_select_info)
+    sig = {
+        "vr_mask_label_device": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li, vp]),
+        "vr_mask_label": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li]),
+        "vr_mask_select_device": (i32, [vp, ext, req, vp, u32, vp, u64, si, vp]),
+        "vr_mask_select": (i32, [vp, ext, req, vp, u32, vp, u64, si]),
+        "vr_maskcc_last_kernel_name": (C.c_char_p, [vp]),
+        "vr_debug_maskcc_pass_ms": (i32, [vp, C.POINTER(C.c_float)]),  # (a debug hook, in no header)
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _MASKCC_LIB = L
+    return L
+
+
+def mask_select_request(rule: int, connectivity: int = 6, min_voxels: int = 0, seed=(0, 0, 0)) -> vr_mask_select_request:
+    """A vr_mask_select_request; seed: the (i, j, k) grid voxel of MASK_KEEP_SEED."""
+    req = vr_mask_select_request()
+    req.rule = int(rule) & 0xFFFFFFFF
+    req.connectivity = int(connectivity) & 0xFFFFFFFF
+    req.min_voxels = int(min_voxels)
+    req.seed[:] = [int(v) & 0xFFFFFFFF for v in seed]
+    return req
 
 
 def mpr_plane(origin, du, dv, dn, width: int, height: int, nsamples: int = 1,
@@ -1121,6 +1182,77 @@ class OffscreenPass:
 
     def morph_last_kernel_name(self) -> str:
         return morph_lib().vr_morph_last_kernel_name(self._ctx).decode()
+
+    # -- the components of a mask: labels, selection, hole filling (vr_maskcc.h, lib/libvr_amd_maskcc.so) --
+    @staticmethod
+    def _select_info(info: vr_mask_select_info) -> dict:
+        return {"voxels": info.voxels, "in_set": info.in_set, "out_set": info.out_set,
+                "components": info.components, "kept": info.kept}
+
+    def mask_label(self, mask, connectivity=6):
+        """vr_mask_label: (labels (bz, by, bx) uint32, records as LABEL_COMPONENT_DTYPE sorted by
+        label, info dict) of a (bz, by, bx) uint8 or uint32 mask.  One labelling where the table has
+        at most 65536 records; a larger one is sized by the first call's VR_ENOSPC info and labelled
+        once more."""
+        m, ext, eb = self._morph_mask(mask)
+        info = vr_label_info()
+        labels = np.zeros(max(m.size, 1), np.uint32)  # (never a NULL buffer)
+        cap = 1 << 16
+        comps = np.zeros(cap, LABEL_COMPONENT_DTYPE)
+        call = lambda: maskcc_lib().vr_mask_label(self._ctx, ext, m.ctypes.data, eb, int(connectivity),
+                                                  labels.ctypes.data, m.size, comps.ctypes.data, cap, C.byref(info))
+        rc = call()
+        if rc == ENOSPC and int(info.voxels) == m.size and int(info.components) > cap:
+            cap = int(info.components)
+            comps = np.zeros(cap, LABEL_COMPONENT_DTYPE)
+            rc = call()
+        self._check(rc, "mask_label")
+        return labels[:m.size].reshape(m.shape), comps[:int(info.components)], self._label_info(info)
+
+    def mask_label_device(self, ext, mask_ptr: int, elem_bytes: int, labels_ptr: int, lcap: int, comps_ptr: int,
+                          ccap: int, connectivity=6, stream: int = 0) -> dict:
+        """vr_mask_label_device: lcap labels and ccap records into device memory on `stream`; returns
+        the info dict when both buffers are complete.  ext: (bx, by, bz)."""
+        info = vr_label_info()
+        self._check(maskcc_lib().vr_mask_label_device(
+            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.c_void_p(mask_ptr), int(elem_bytes),
+            int(connectivity), C.c_void_p(labels_ptr), int(lcap), C.c_void_p(comps_ptr), int(ccap), C.byref(info),
+            C.c_void_p(stream or None)), "mask_label_device")
+        return self._label_info(info)
+
+    def mask_select(self, mask, rule: int, connectivity=6, min_voxels: int = 0, seed=(0, 0, 0)) -> dict:
+        """vr_mask_select: {"mask": (bz, by, bx) uint8 of 0/1, "info": dict} -- MASK_KEEP_LARGEST,
+        _KEEP_MIN_VOXELS, _KEEP_SEED (seed: the (i, j, k) grid voxel) or MASK_FILL_HOLES."""
+        m, ext, eb = self._morph_mask(mask)
+        req = mask_select_request(rule, connectivity, min_voxels, seed)
+        out = np.zeros(max(m.size, 1), np.uint8)  # (never a NULL buffer)
+        info = vr_mask_select_info()
+        self._check(maskcc_lib().vr_mask_select(self._ctx, ext, C.byref(req), m.ctypes.data, eb, out.ctypes.data,
+                                                m.size, C.byref(info)), "mask_select")
+        return {"mask": out[:m.size].reshape(m.shape), "info": self._select_info(info)}
+
+    def mask_select_device(self, ext, rule: int, mask_ptr: int, elem_bytes: int, out_ptr: int, mcap: int,
+                           connectivity=6, min_voxels: int = 0, seed=(0, 0, 0), stream: int = 0) -> dict:
+        """vr_mask_select_device: mcap mask bytes into device memory on `stream`; returns the info
+        dict when the buffer is complete.  ext: (bx, by, bz)."""
+        req = mask_select_request(rule, connectivity, min_voxels, seed)
+        info = vr_mask_select_info()
+        self._check(maskcc_lib().vr_mask_select_device(
+            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.byref(req), C.c_void_p(mask_ptr),
+            int(elem_bytes), C.c_void_p(out_ptr), int(mcap), C.byref(info), C.c_void_p(stream or None)),
+            "mask_select_device")
+        return self._select_info(info)
+
+    MASKCC_PASSES = ("rows", "link", "flatten", "scan", "table_init", "accumulate", "largest", "keep", "select")
+
+    def maskcc_pass_ms(self) -> dict:
+        """Kernel ms of each pass of the last mask_label* or mask_select* call (timing enabled), by name."""
+        ms = (C.c_float * 9)()
+        self._check(maskcc_lib().vr_debug_maskcc_pass_ms(self._ctx, ms), "maskcc_pass_ms")
+        return dict(zip(self.MASKCC_PASSES, (float(v) for v in ms)))
+
+    def maskcc_last_kernel_name(self) -> str:
+        return maskcc_lib().vr_maskcc_last_kernel_name(self._ctx).decode()
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
