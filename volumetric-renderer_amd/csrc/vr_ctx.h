@@ -175,6 +175,13 @@ struct vr_ctx {
     // kernel ms of the last call's passes (vr_maskcc_kernels.h MccPass), taken while timing is
     // enabled; 0 for a pass that call did not run (vr_debug_maskcc_pass_ms, csrc/vr_api_maskcc.hip)
     float maskcc_pass_ms[9] = {};
+    // vr_mask_stats*, vr_label_stats*, vr_mask_window* (vr_mstat.h; csrc/vr_api_mstat.hip in
+    // lib/libvr_amd_mstat.so): the counters, the histogram's counts and edges and per record its
+    // accumulators, its record and its compacted label (vr_mstat_host.h MstatGeom), and the host
+    // forms' device copies of their arrays; both grown on demand.  mstat_last_name: the family's last
+    // kernel (vr_mstat_last_kernel_name)
+    DevBlock mstat_aux_dev, mstat_io_dev;
+    const char *mstat_last_name = "";
     // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
     // taken while timing is enabled; 0 for a pass that call did not run
     float label_pass_ms[kLabelPassSlots] = {};

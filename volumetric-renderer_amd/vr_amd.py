@@ -165,6 +165,16 @@ class vr_mask_select_info(C.Structure):  # vr_maskcc.h
                 ("components", C.c_uint64), ("kept", C.c_uint64)]
 
 
+class vr_mstat_region(C.Structure):  # vr_mstat.h
+    _fields_ = [("label", C.c_uint32), ("reserved", C.c_uint32), ("voxels", C.c_uint64), ("nan", C.c_uint64),
+                ("vmin", C.c_float), ("vmax", C.c_float), ("min_index", C.c_uint32), ("max_index", C.c_uint32),
+                ("sum", C.c_double), ("sum2", C.c_double), ("reserved2", C.c_uint64)]
+
+
+class vr_mstat_info(C.Structure):  # vr_mstat.h
+    _fields_ = [("voxels", C.c_uint64), ("set", C.c_uint64), ("unlisted", C.c_uint64), ("regions", C.c_uint64)]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -247,6 +257,15 @@ MASKCC_SYMBOLS = ["vr_mask_label", "vr_mask_label_device", "vr_mask_select", "vr
                   "vr_maskcc_last_kernel_name"]
 MASK_KEEP_LARGEST, MASK_KEEP_MIN_VOXELS, MASK_KEEP_SEED, MASK_FILL_HOLES = 0, 1, 2, 3
 MASKCC_MAX_EXTENT = 32768
+# include/vr/vr_mstat.h: the statistics of the volume under a mask or a label array and the value-window
+# pass; the entry points live in a fourth library, lib/libvr_amd_mstat.so (mstat_lib()), on the same context
+MSTAT_SYMBOLS = ["vr_mask_stats", "vr_mask_stats_device", "vr_label_stats", "vr_label_stats_device",
+                 "vr_mask_window", "vr_mask_window_device", "vr_mstat_last_kernel_name"]
+MSTAT_REGION_DTYPE = np.dtype([("label", "<u4"), ("reserved", "<u4"), ("voxels", "<u8"), ("nan", "<u8"),
+                               ("vmin", "<f4"), ("vmax", "<f4"), ("min_index", "<u4"), ("max_index", "<u4"),
+                               ("sum", "<f8"), ("sum2", "<f8"), ("reserved2", "<u8")])
+MSTAT_NONE = 0xFFFFFFFF
+MSTAT_MAX_EXTENT = 32768
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -481,6 +500,48 @@ def maskcc_lib() -> C.CDLL:
         fn.argtypes = args
     _MASKCC_LIB = L
     return L
+
+
+MSTAT_LIB_PATH = os.environ.get("VR_AMD_MSTAT_LIB") or os.path.join(os.path.dirname(LIB_PATH),
+                                                                    "libvr_amd_mstat.so")
+_MSTAT_LIB = None
+
+
+def mstat_lib() -> C.CDLL:
+    """Load lib/libvr_amd_mstat.so (vr_mstat.h) on first use, after lib(): it takes the host
+    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
+    global _MSTAT_LIB
+    if _MSTAT_LIB is not None:
+        return _MSTAT_LIB
+    lib()
+    if not os.path.exists(MSTAT_LIB_PATH):
+        raise RuntimeError(f"{MSTAT_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
+                           "(or __graft_entry__.build()); there is no CPU fallback")
+    L = C.CDLL(MSTAT_LIB_PATH)
+    vp, u32, u64, i32, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_float
+    ext = C.POINTER(u32)
+    hr, hi, mi, wi = (C.POINTER(vr_hist_request), C.POINTER(vr_hist_info), C.POINTER(vr_mstat_info),
+                      C.POINTER(vr_morph_info))
+    sig = {
+        "vr_mask_stats_device": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, C.POINTER(vr_mstat_region), vp]),
+        "vr_mask_stats": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, C.POINTER(vr_mstat_region)]),
+        "vr_label_stats_device": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, mi, vp]),
+        "vr_label_stats": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, mi]),
+        "vr_mask_window_device": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, wi, vp]),
+        "vr_mask_window": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, wi]),
+        "vr_mstat_last_kernel_name": (C.c_char_p, [vp]),
+    }
+    for name, (res, args) in sig.items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _MSTAT_LIB = L
+    return L
+
+
+def mstat_region_dict(r: vr_mstat_region) -> dict:
+    return {"label": r.label, "voxels": r.voxels, "nan": r.nan, "vmin": r.vmin, "vmax": r.vmax,
+            "min_index": r.min_index, "max_index": r.max_index, "sum": r.sum, "sum2": r.sum2}
 
 
 def mask_select_request(rule: int, connectivity: int = 6, min_voxels: int = 0, seed=(0, 0, 0)) -> vr_mask_select_request:
@@ -1253,6 +1314,116 @@ class OffscreenPass:
 
     def maskcc_last_kernel_name(self) -> str:
         return maskcc_lib().vr_maskcc_last_kernel_name(self._ctx).decode()
+
+    # -- the volume under a mask or a label array (vr_mstat.h, lib/libvr_amd_mstat.so) --
+    @staticmethod
+    def _u3(v):
+        return (C.c_uint32 * 3)(*[int(x) & 0xFFFFFFFF for x in v])
+
+    @staticmethod
+    def _mstat_hist(hist):
+        """hist = (nbins, lo, hi) or None -> (request or None, bins or None, info or None)."""
+        if hist is None:
+            return None, None, None
+        req = vr_hist_request()
+        req.nbins, req.lo, req.hi = int(hist[0]), float(hist[1]), float(hist[2])
+        return req, np.zeros(min(max(int(hist[0]), 1), HIST_MAX_BINS), np.uint64), vr_hist_info()
+
+    @staticmethod
+    def _mstat_stats_result(region, bins, hinfo) -> dict:
+        out = {"region": mstat_region_dict(region)}
+        if bins is not None:
+            out["bins"] = bins
+            out["hist_info"] = {"voxels": hinfo.voxels, "below": hinfo.below, "above": hinfo.above,
+                                "nan": hinfo.nan, "vmin": np.float32(hinfo.vmin), "vmax": np.float32(hinfo.vmax)}
+        return out
+
+    @staticmethod
+    def _mstat_info(info: vr_mstat_info) -> dict:
+        return {"voxels": info.voxels, "set": info.set, "unlisted": info.unlisted, "regions": info.regions}
+
+    def mask_stats(self, mask, origin=(0, 0, 0), hist=None) -> dict:
+        """vr_mask_stats: {"region": dict, and with hist = (nbins, lo, hi) "bins": uint64 counts,
+        "hist_info": dict} of the volume under a (bz, by, bx) uint8 or uint32 mask whose voxel
+        (0, 0, 0) is the volume voxel origin = (x, y, z)."""
+        m, ext, eb = self._morph_mask(mask)
+        req, bins, hinfo = self._mstat_hist(hist)
+        region = vr_mstat_region()
+        self._check(mstat_lib().vr_mask_stats(
+            self._ctx, ext, self._u3(origin), m.ctypes.data, eb, C.byref(req) if req is not None else None,
+            bins.ctypes.data if bins is not None else None, C.byref(hinfo) if hinfo is not None else None,
+            C.byref(region)), "mask_stats")
+        return self._mstat_stats_result(region, bins, hinfo)
+
+    def mask_stats_device(self, ext, mask_ptr: int, elem_bytes: int, origin=(0, 0, 0), hist=None,
+                          stream: int = 0) -> dict:
+        """vr_mask_stats_device: the same of a mask in device memory, on `stream`.  ext: (bx, by, bz)."""
+        req, bins, hinfo = self._mstat_hist(hist)
+        region = vr_mstat_region()
+        self._check(mstat_lib().vr_mask_stats_device(
+            self._ctx, self._u3(ext), self._u3(origin), C.c_void_p(mask_ptr), int(elem_bytes),
+            C.byref(req) if req is not None else None, bins.ctypes.data if bins is not None else None,
+            C.byref(hinfo) if hinfo is not None else None, C.byref(region), C.c_void_p(stream or None)),
+            "mask_stats_device")
+        return self._mstat_stats_result(region, bins, hinfo)
+
+    def label_stats(self, labels, table, origin=(0, 0, 0)):
+        """vr_label_stats: (records as MSTAT_REGION_DTYPE in table order, info dict) of a (bz, by, bx)
+        uint32 label array and a table of LABEL_COMPONENT_DTYPE records (only "label" is read)."""
+        lab = np.ascontiguousarray(labels)
+        if lab.ndim != 3 or lab.dtype != np.dtype(np.uint32):
+            raise ValueError("a label array is a (bz, by, bx) array of uint32")
+        tab = np.ascontiguousarray(table, LABEL_COMPONENT_DTYPE)
+        n = int(tab.size)
+        tab_buf = tab if n else np.zeros(1, LABEL_COMPONENT_DTYPE)  # (never a NULL buffer)
+        out = np.zeros(max(n, 1), MSTAT_REGION_DTYPE)
+        info = vr_mstat_info()
+        self._check(mstat_lib().vr_label_stats(
+            self._ctx, self._u3(lab.shape[::-1]), self._u3(origin), lab.ctypes.data, tab_buf.ctypes.data, n,
+            out.ctypes.data, n, C.byref(info)), "label_stats")
+        return out[:n], self._mstat_info(info)
+
+    def label_stats_device(self, ext, labels_ptr: int, table_ptr: int, ntable: int, regions_ptr: int, rcap: int,
+                           origin=(0, 0, 0), stream: int = 0) -> dict:
+        """vr_label_stats_device: ntable records into device memory (rcap records) on `stream`; returns
+        the info dict when they are complete.  ext: (bx, by, bz)."""
+        info = vr_mstat_info()
+        self._check(mstat_lib().vr_label_stats_device(
+            self._ctx, self._u3(ext), self._u3(origin), C.c_void_p(labels_ptr), C.c_void_p(table_ptr), int(ntable),
+            C.c_void_p(regions_ptr), int(rcap), C.byref(info), C.c_void_p(stream or None)), "label_stats_device")
+        return self._mstat_info(info)
+
+    def mask_window(self, mask, lo: float, hi: float, origin=(0, 0, 0), shape=None) -> dict:
+        """vr_mask_window: {"mask": (bz, by, bx) uint8 of 0/1, "info": dict} -- the voxels of `mask`
+        (None: of the whole (bz, by, bx) = shape grid) with lo <= f <= hi."""
+        if mask is None:
+            m, eb = None, 1
+            shp = tuple(int(v) for v in shape)
+            ext = self._u3(shp[::-1])
+        else:
+            m, ext, eb = self._morph_mask(mask)
+            shp = m.shape
+        n = shp[0] * shp[1] * shp[2]
+        out = np.zeros(max(n, 1), np.uint8)  # (never a NULL buffer)
+        info = vr_morph_info()
+        self._check(mstat_lib().vr_mask_window(
+            self._ctx, ext, self._u3(origin), m.ctypes.data if m is not None else None, eb, float(lo), float(hi),
+            out.ctypes.data, n, C.byref(info)), "mask_window")
+        return {"mask": out[:n].reshape(shp), "info": self._morph_info(info)}
+
+    def mask_window_device(self, ext, mask_ptr: int, elem_bytes: int, lo: float, hi: float, out_ptr: int, mcap: int,
+                           origin=(0, 0, 0), stream: int = 0) -> dict:
+        """vr_mask_window_device: mcap mask bytes into device memory on `stream` (mask_ptr 0: every
+        grid voxel is set); returns the info dict when the buffer is complete.  ext: (bx, by, bz)."""
+        info = vr_morph_info()
+        self._check(mstat_lib().vr_mask_window_device(
+            self._ctx, self._u3(ext), self._u3(origin), C.c_void_p(mask_ptr or None), int(elem_bytes), float(lo),
+            float(hi), C.c_void_p(out_ptr), int(mcap), C.byref(info), C.c_void_p(stream or None)),
+            "mask_window_device")
+        return self._morph_info(info)
+
+    def mstat_last_kernel_name(self) -> str:
+        return mstat_lib().vr_mstat_last_kernel_name(self._ctx).decode()
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
