@@ -24,8 +24,8 @@ static int g_bad = 0;
 
 static_assert(sizeof(vr_mask_select_request) == 32 && sizeof(vr_mask_select_info) == 40, "vr_maskcc.h structs");
 static_assert(sizeof(vr_label_component) == kMccRecordBytes && sizeof(vr_label_info) == 40, "vr_label.h structs");
-static_assert(VR_MASKCC_MAX_EXTENT == kMccMaxExtent, "vr_maskcc.h constants");
-static_assert(VR_EINVAL == kMccEinval && VR_ENOSPC == kMccEnospc && VR_OK == kMccOk, "codes");
+static_assert(VR_MASKCC_MAX_EXTENT == kMaskMaxExtent, "vr_maskcc.h constants");
+static_assert(VR_EINVAL == kMaskEinval && VR_ENOSPC == kMaskEnospc && VR_OK == kMaskOk, "codes");
 static_assert(VR_MASK_FILL_HOLES + 1 == kMccRules && VR_MASK_KEEP_SEED == kMccKeepSeed &&
                   VR_MASK_KEEP_LARGEST == kMccKeepLargest && VR_MASK_KEEP_MIN_VOXELS == kMccKeepMinVoxels &&
                   VR_MASK_FILL_HOLES == kMccFillHoles, "enum vr_mask_rule");
@@ -34,10 +34,10 @@ static void grid_case(uint32_t bx, uint32_t by, uint32_t bz)
 {
     // the array sits at the very end of a heap block: a read past [2] is an ASan report
     std::vector<uint32_t> ext{bx, by, bz};
-    MccGrid g;
+    MaskGrid g;
     std::memset(&g, 0x77, sizeof g);
-    const MccGrid before = g;
-    const char *m = mcc_grid_resolve(ext.data(), &g);
+    const MaskGrid before = g;
+    const char *m = kMccTexts[mask_grid_resolve(ext.data(), &g)];
     bool want = true;
     unsigned long long vox = 1;
     for (uint32_t e : ext) {
@@ -80,11 +80,11 @@ int main()
 
     {  // alignment and overlap
         alignas(8) static unsigned char buf[64] = {0};
-        CHECK(mcc_aligned4(buf) && mcc_aligned4(buf + 4) && !mcc_aligned4(buf + 1) && !mcc_aligned4(buf + 2) &&
-              !mcc_aligned4(buf + 3));
-        CHECK(mcc_overlap(buf, 8, buf, 8) && mcc_overlap(buf, 8, buf + 7, 1) && mcc_overlap(buf + 7, 1, buf, 8));
-        CHECK(!mcc_overlap(buf, 8, buf + 8, 8) && !mcc_overlap(buf + 8, 8, buf, 8));
-        CHECK(mcc_overlap(buf, 64, buf + 20, 4) && mcc_overlap(buf + 20, 4, buf, 64));
+        CHECK(mask_aligned4(buf) && mask_aligned4(buf + 4) && !mask_aligned4(buf + 1) && !mask_aligned4(buf + 2) &&
+              !mask_aligned4(buf + 3));
+        CHECK(mask_overlap(buf, 8, buf, 8) && mask_overlap(buf, 8, buf + 7, 1) && mask_overlap(buf + 7, 1, buf, 8));
+        CHECK(!mask_overlap(buf, 8, buf + 8, 8) && !mask_overlap(buf + 8, 8, buf, 8));
+        CHECK(mask_overlap(buf, 64, buf + 20, 4) && mask_overlap(buf + 20, 4, buf, 64));
     }
     {  // the request checks: every refusal leaves the grid untouched; ENOSPC resolves it
         alignas(8) static unsigned char mask[4 * 24 + 8], out[4 * 24 + 64 * 24 + 8];  // (labels, then records)
@@ -92,10 +92,10 @@ int main()
         vr_label_info li;
         vr_mask_select_info si;
         const char *msg = nullptr;
-        MccGrid g;
+        MaskGrid g;
         auto fresh = [&] { std::memset(&g, 0x77, sizeof g); };
         auto untouched = [&] {
-            MccGrid f;
+            MaskGrid f;
             std::memset(&f, 0x77, sizeof f);
             return std::memcmp(&g, &f, sizeof g) == 0;
         };

@@ -22,8 +22,8 @@ static int g_bad = 0;
     } while (0)
 
 static_assert(sizeof(vr_edt_info) == 24 && sizeof(vr_morph_info) == 24, "vr_morph.h infos are 24 bytes");
-static_assert(VR_EDT_NONE == kMorphNone && VR_MORPH_MAX_EXTENT == kMorphMaxExtent, "vr_morph.h constants");
-static_assert(VR_EINVAL == kMorphEinval && VR_ENOSPC == kMorphEnospc && VR_OK == kMorphOk, "codes");
+static_assert(VR_EDT_NONE == kMorphNone && VR_MORPH_MAX_EXTENT == kMaskMaxExtent, "vr_morph.h constants");
+static_assert(VR_EINVAL == kMaskEinval && VR_ENOSPC == kMaskEnospc && VR_OK == kMaskOk, "codes");
 static_assert(VR_MORPH_CLOSE + 1 == kMorphOps && VR_EDT_TO_UNSET + 1 == kMorphTargets, "enums");
 static_assert(3ull * 32767 * 32767 < VR_EDT_NONE, "the largest distance stays below the sentinel");
 
@@ -31,10 +31,10 @@ static void grid_case(uint32_t bx, uint32_t by, uint32_t bz)
 {
     // the array sits at the very end of a heap block: a read past [2] is an ASan report
     std::vector<uint32_t> ext{bx, by, bz};
-    MorphGrid g;
+    MaskGrid g;
     std::memset(&g, 0x77, sizeof g);
-    const MorphGrid before = g;
-    const char *m = morph_grid_resolve(ext.data(), &g);
+    const MaskGrid before = g;
+    const char *m = kMorphTexts[mask_grid_resolve(ext.data(), &g)];
     bool want = true;
     unsigned long long vox = 1;
     for (uint32_t e : ext) {
@@ -78,11 +78,11 @@ int main()
 
     {  // alignment and overlap
         alignas(8) static unsigned char buf[64] = {0};
-        CHECK(morph_aligned4(buf) && morph_aligned4(buf + 4) && !morph_aligned4(buf + 1) && !morph_aligned4(buf + 2) &&
-              !morph_aligned4(buf + 3));
-        CHECK(morph_overlap(buf, 8, buf, 8) && morph_overlap(buf, 8, buf + 7, 1) && morph_overlap(buf + 7, 1, buf, 8));
-        CHECK(!morph_overlap(buf, 8, buf + 8, 8) && !morph_overlap(buf + 8, 8, buf, 8));
-        CHECK(morph_overlap(buf, 64, buf + 20, 4) && morph_overlap(buf + 20, 4, buf, 64));
+        CHECK(mask_aligned4(buf) && mask_aligned4(buf + 4) && !mask_aligned4(buf + 1) && !mask_aligned4(buf + 2) &&
+              !mask_aligned4(buf + 3));
+        CHECK(mask_overlap(buf, 8, buf, 8) && mask_overlap(buf, 8, buf + 7, 1) && mask_overlap(buf + 7, 1, buf, 8));
+        CHECK(!mask_overlap(buf, 8, buf + 8, 8) && !mask_overlap(buf + 8, 8, buf, 8));
+        CHECK(mask_overlap(buf, 64, buf + 20, 4) && mask_overlap(buf + 20, 4, buf, 64));
     }
     {  // the request checks: every refusal leaves the grid untouched; ENOSPC resolves it
         alignas(8) static unsigned char mask[4 * 24 + 8], out[4 * 24 + 8];
@@ -90,10 +90,10 @@ int main()
         vr_edt_info ei;
         vr_morph_info mi;
         const char *msg = nullptr;
-        MorphGrid g;
+        MaskGrid g;
         auto fresh = [&] { std::memset(&g, 0x77, sizeof g); };
         auto untouched = [&] {
-            MorphGrid f;
+            MaskGrid f;
             std::memset(&f, 0x77, sizeof f);
             return std::memcmp(&g, &f, sizeof g) == 0;
         };

@@ -26,18 +26,18 @@ static int g_bad = 0;
 
 static_assert(sizeof(vr_mstat_region) == 64 && sizeof(vr_mstat_info) == 32, "vr_mstat.h structs");
 static_assert(sizeof(vr_mstat_region) == kMstatRecordBytes && sizeof(vr_label_component) == kMstatRecordBytes, "records");
-static_assert(VR_MSTAT_MAX_EXTENT == kMstatMaxExtent && VR_MSTAT_NONE == kMstatNone, "vr_mstat.h constants");
-static_assert(VR_EINVAL == kMstatEinval && VR_ENOSPC == kMstatEnospc && VR_OK == kMstatOk, "codes");
+static_assert(VR_MSTAT_MAX_EXTENT == kMaskMaxExtent && VR_MSTAT_NONE == kMstatNone, "vr_mstat.h constants");
+static_assert(VR_EINVAL == kMaskEinval && VR_ENOSPC == kMaskEnospc && VR_OK == kMaskOk, "codes");
 static_assert(VR_HIST_MAX_BINS == kHistMaxBins, "vr_hist.h");
 
 static void grid_case(uint32_t bx, uint32_t by, uint32_t bz, uint64_t nrec)
 {
     // the array sits at the very end of a heap block: a read past [2] is an ASan report
     std::vector<uint32_t> ext{bx, by, bz};
-    MstatGrid g;
+    MaskGrid g;
     std::memset(&g, 0x77, sizeof g);
-    const MstatGrid before = g;
-    const char *m = mstat_grid_resolve(ext.data(), &g);
+    const MaskGrid before = g;
+    const char *m = kMstatTexts[mask_grid_resolve(ext.data(), &g)];
     bool want = true;
     unsigned long long vox = 1;
     for (uint32_t e : ext) {
@@ -138,16 +138,16 @@ int main()
 
     {  // alignment and overlap
         alignas(8) static unsigned char buf[64] = {0};
-        CHECK(mstat_aligned4(buf) && mstat_aligned4(buf + 4) && !mstat_aligned4(buf + 1) && !mstat_aligned4(buf + 2) &&
-              !mstat_aligned4(buf + 3));
-        CHECK(mstat_overlap(buf, 8, buf, 8) && mstat_overlap(buf, 8, buf + 7, 1) && mstat_overlap(buf + 7, 1, buf, 8));
-        CHECK(!mstat_overlap(buf, 8, buf + 8, 8) && !mstat_overlap(buf + 8, 8, buf, 8));
-        CHECK(mstat_overlap(buf, 64, buf + 20, 4) && mstat_overlap(buf + 20, 4, buf, 64));
+        CHECK(mask_aligned4(buf) && mask_aligned4(buf + 4) && !mask_aligned4(buf + 1) && !mask_aligned4(buf + 2) &&
+              !mask_aligned4(buf + 3));
+        CHECK(mask_overlap(buf, 8, buf, 8) && mask_overlap(buf, 8, buf + 7, 1) && mask_overlap(buf + 7, 1, buf, 8));
+        CHECK(!mask_overlap(buf, 8, buf + 8, 8) && !mask_overlap(buf + 8, 8, buf, 8));
+        CHECK(mask_overlap(buf, 64, buf + 20, 4) && mask_overlap(buf + 20, 4, buf, 64));
     }
     {  // the grid against the volume
-        MstatGrid g;
+        MaskGrid g;
         const uint32_t ext[3] = {4, 3, 2}, dims[3] = {10, 9, 8};
-        CHECK(!mstat_grid_resolve(ext, &g));
+        CHECK(!mask_grid_resolve(ext, &g));
         const uint32_t ok[][3] = {{0, 0, 0}, {6, 6, 6}, {6, 0, 0}, {0, 6, 0}, {0, 0, 6}};
         const uint32_t bad[][3] = {{7, 0, 0}, {0, 7, 0}, {0, 0, 7}, {M, 0, 0}, {0, M - 1, 0}, {0, 0, M - 2}, {M, M, M}, {10, 9, 8}};
         for (const auto &o : ok) {
@@ -169,10 +169,10 @@ int main()
         vr_hist_info hi;
         uint64_t bins[8];
         const char *msg = nullptr;
-        MstatGrid g;
+        MaskGrid g;
         auto fresh = [&] { std::memset(&g, 0x77, sizeof g); };
         auto untouched = [&] {
-            MstatGrid f;
+            MaskGrid f;
             std::memset(&f, 0x77, sizeof f);
             return std::memcmp(&g, &f, sizeof g) == 0;
         };

@@ -1,14 +1,14 @@
 // vr_api_maskcc.hip — the components of a mask: labels, records, selection and hole filling
-// (include/vr/vr_maskcc.h) on the host scaffold of vr_ctx.h.  Built into lib/libvr_amd_maskcc.so,
+// (include/vr/vr_maskcc.h) on the host scaffold of vr_ctx.h and vr_mask_call.h.  Built into lib/libvr_amd_maskcc.so,
 // which takes the scaffold (fail, hip_fail, reserve, pooled_event, the group's wait) from
 // libvr_amd.so.
-#include "vr_ctx.h"
+#include "vr_mask_call.h"
 #include "../../include/vr/vr_maskcc.h"
 #include "vr_maskcc_kernels.h"
 
 namespace {
-static_assert(VR_MASKCC_MAX_EXTENT == kMccMaxExtent && VR_EINVAL == kMccEinval && VR_ENOSPC == kMccEnospc &&
-                  VR_OK == kMccOk && VR_MASK_FILL_HOLES + 1 == kMccRules && VR_MASK_KEEP_LARGEST == kMccKeepLargest &&
+static_assert(VR_MASKCC_MAX_EXTENT == kMaskMaxExtent && VR_MASK_FILL_HOLES + 1 == kMccRules &&
+                  VR_MASK_KEEP_LARGEST == kMccKeepLargest &&
                   VR_MASK_KEEP_MIN_VOXELS == kMccKeepMinVoxels && VR_MASK_KEEP_SEED == kMccKeepSeed &&
                   VR_MASK_FILL_HOLES == kMccFillHoles && sizeof(vr_mask_select_request) == 32 &&
                   sizeof(vr_mask_select_info) == 40 && sizeof(vr_label_component) == kMccRecordBytes &&
@@ -25,7 +25,7 @@ constexpr const char *kMccIdle = "hipDeviceSynchronize (maskcc scratch)";
 struct MccRun {
     vr_ctx *c;
     hipStream_t s;
-    MccGrid g;
+    MaskGrid g;
     MccArgs A;
     uint32_t conn = 0;
     Interval timed;
@@ -170,9 +170,6 @@ struct MccRun {
     }
 };
 
-// The host forms' device copies: the mask at the block's start, the result behind it, 4-byte aligned.
-size_t io_result_offset(const MccGrid &g, uint32_t elem_bytes) { return ((size_t)g.voxels * elem_bytes + 3) & ~(size_t)3; }
-
 constexpr const char *kCcapMsg = "record buffer is smaller than the table (see the info's components)";
 }  // namespace
 
@@ -182,119 +179,105 @@ int vr_mask_label_device(vr_ctx *c, const uint32_t ext[3], const void *mask_dev,
                          uint32_t connectivity, void *labels_dev, uint64_t lcap, void *comps_dev, uint64_t ccap,
                          vr_label_info *info, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MccRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = mcc_check_label(ext, mask_dev, elem_bytes, connectivity, labels_dev, lcap, comps_dev, ccap, info,
-                                   true, &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_label_info{R.g.voxels};  // known on the host: the voxels alone, every other field 0
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mcc_check_label(ext, mask_dev, elem_bytes, connectivity, labels_dev, lcap, comps_dev, ccap, info,
+                                   true, &R.g, msg);
+        },
+        [&](vr_ctx *m) {
             return vr_mask_label_device(m, ext, mask_dev, elem_bytes, connectivity, labels_dev, lcap, comps_dev, ccap,
                                         info, stream);
+        },
+        nullptr,
+        [&](vr_label_info *I) {
+            if (int rc = R.begin(mask_dev, elem_bytes, connectivity, false, labels_dev)) return rc;
+            if (int rc = R.label(I)) return rc;
+            if (int rc = R.table(I)) return rc;
+            if (ccap < I->components) {
+                *info = *I;
+                return fail(c, VR_ENOSPC, kCcapMsg);
+            }
+            if (I->components) {
+                HIP_TRY(c, hipMemcpyAsync(comps_dev, R.A.comps, (size_t)I->components * kMccRecordBytes,
+                                          hipMemcpyDeviceToDevice, R.s), "hipMemcpy(maskcc records)");
+                HIP_TRY(c, hipStreamSynchronize(R.s), "hipStreamSynchronize(maskcc records)");
+            }
+            return VR_OK;
         });
-    vr_label_info I;
-    if (int rc2 = R.begin(mask_dev, elem_bytes, connectivity, false, labels_dev)) return rc2;
-    if (int rc2 = R.label(&I)) return rc2;
-    if (int rc2 = R.table(&I)) return rc2;
-    if (ccap < I.components) {
-        *info = I;
-        return fail(c, VR_ENOSPC, kCcapMsg);
-    }
-    if (I.components) {
-        HIP_TRY(c, hipMemcpyAsync(comps_dev, R.A.comps, (size_t)I.components * kMccRecordBytes, hipMemcpyDeviceToDevice,
-                                  R.s), "hipMemcpy(maskcc records)");
-        HIP_TRY(c, hipStreamSynchronize(R.s), "hipStreamSynchronize(maskcc records)");
-    }
-    *info = I;
-    return VR_OK;
 }
 
 int vr_mask_label(vr_ctx *c, const uint32_t ext[3], const void *mask_host, uint32_t elem_bytes, uint32_t connectivity,
                   uint32_t *labels_host, uint64_t lcap, vr_label_component *comps_host, uint64_t ccap,
                   vr_label_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MccRun R{c, nullptr};
-    const char *msg;
-    const int rc = mcc_check_label(ext, mask_host, elem_bytes, connectivity, labels_host, lcap, comps_host, ccap, info,
-                                   false, &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_label_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mcc_check_label(ext, mask_host, elem_bytes, connectivity, labels_host, lcap, comps_host, ccap, info,
+                                   false, &R.g, msg);
+        },
+        [&](vr_ctx *m) {
             return vr_mask_label(m, ext, mask_host, elem_bytes, connectivity, labels_host, lcap, comps_host, ccap, info);
+        },
+        nullptr,
+        [&](vr_label_info *I) {
+            MaskStage S{c};
+            if (int rc = S.begin(c->maskcc_io_dev, "hipMalloc(maskcc staging)", kMccIdle,
+                                 {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {},
+                                 (size_t)R.g.voxels * 4))
+                return rc;
+            if (int rc = R.begin(S.in[0], elem_bytes, connectivity, false, S.out)) return rc;
+            if (int rc = R.label(I)) return rc;
+            if (int rc = R.table(I)) return rc;
+            if (int rc = S.finish(labels_host, "hipMemcpy(labels)")) return rc;
+            if (ccap < I->components) {
+                *info = *I;
+                return fail(c, VR_ENOSPC, kCcapMsg);
+            }
+            if (I->components)
+                HIP_TRY(c, hipMemcpy(comps_host, R.A.comps, (size_t)I->components * kMccRecordBytes, hipMemcpyDeviceToHost),
+                        "hipMemcpy(maskcc records)");
+            return VR_OK;
         });
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t in_bytes = (size_t)R.g.voxels * elem_bytes, off = io_result_offset(R.g, elem_bytes);
-    if (int rc2 = reserve(c, c->maskcc_io_dev, off + (size_t)R.g.voxels * 4, "hipMalloc(maskcc staging)", kMccIdle))
-        return rc2;
-    char *io = static_cast<char *>(c->maskcc_io_dev.p);
-    HIP_TRY(c, hipMemcpy(io, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    vr_label_info I;
-    if (int rc2 = R.begin(io, elem_bytes, connectivity, false, io + off)) return rc2;
-    if (int rc2 = R.label(&I)) return rc2;
-    if (int rc2 = R.table(&I)) return rc2;
-    HIP_TRY(c, hipMemcpy(labels_host, io + off, (size_t)R.g.voxels * 4, hipMemcpyDeviceToHost), "hipMemcpy(labels)");
-    if (ccap < I.components) {
-        *info = I;
-        return fail(c, VR_ENOSPC, kCcapMsg);
-    }
-    if (I.components)
-        HIP_TRY(c, hipMemcpy(comps_host, R.A.comps, (size_t)I.components * kMccRecordBytes, hipMemcpyDeviceToHost),
-                "hipMemcpy(maskcc records)");
-    *info = I;
-    return VR_OK;
 }
 
 int vr_mask_select_device(vr_ctx *c, const uint32_t ext[3], const vr_mask_select_request *req, const void *mask_dev,
                           uint32_t elem_bytes, void *out_dev, uint64_t mcap, vr_mask_select_info *info, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MccRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = mcc_check_select(ext, req != nullptr, req ? req->rule : 0u, req ? req->connectivity : 0u,
-                                    req ? req->seed : nullptr, mask_dev, elem_bytes, out_dev, mcap, info, true, &R.g,
-                                    &msg);
-    if (rc == VR_ENOSPC) *info = vr_mask_select_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_mask_select_device(m, ext, req, mask_dev, elem_bytes, out_dev, mcap, info, stream);
-        });
-    vr_mask_select_info S;
-    if (int rc2 = R.select(req, mask_dev, elem_bytes, out_dev, &S)) return rc2;
-    *info = S;
-    return VR_OK;
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mcc_check_select(ext, req != nullptr, req ? req->rule : 0u, req ? req->connectivity : 0u,
+                                    req ? req->seed : nullptr, mask_dev, elem_bytes, out_dev, mcap, info, true, &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_mask_select_device(m, ext, req, mask_dev, elem_bytes, out_dev, mcap, info, stream); },
+        nullptr, [&](vr_mask_select_info *S) { return R.select(req, mask_dev, elem_bytes, out_dev, S); });
 }
 
 int vr_mask_select(vr_ctx *c, const uint32_t ext[3], const vr_mask_select_request *req, const void *mask_host,
                    uint32_t elem_bytes, uint8_t *out_host, uint64_t mcap, vr_mask_select_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MccRun R{c, nullptr};
-    const char *msg;
-    const int rc = mcc_check_select(ext, req != nullptr, req ? req->rule : 0u, req ? req->connectivity : 0u,
-                                    req ? req->seed : nullptr, mask_host, elem_bytes, out_host, mcap, info, false,
-                                    &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_mask_select_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_mask_select(m, ext, req, mask_host, elem_bytes, out_host, mcap, info);
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mcc_check_select(ext, req != nullptr, req ? req->rule : 0u, req ? req->connectivity : 0u,
+                                    req ? req->seed : nullptr, mask_host, elem_bytes, out_host, mcap, info, false, &R.g,
+                                    msg);
+        },
+        [&](vr_ctx *m) { return vr_mask_select(m, ext, req, mask_host, elem_bytes, out_host, mcap, info); }, nullptr,
+        [&](vr_mask_select_info *I) {
+            MaskStage S{c};
+            if (int rc = S.begin(c->maskcc_io_dev, "hipMalloc(maskcc staging)", kMccIdle,
+                                 {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {}, (size_t)R.g.voxels))
+                return rc;
+            if (int rc = R.select(req, S.in[0], elem_bytes, S.out, I)) return rc;
+            return S.finish(out_host, "hipMemcpy(selected mask)");
         });
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t in_bytes = (size_t)R.g.voxels * elem_bytes, off = io_result_offset(R.g, elem_bytes);
-    if (int rc2 = reserve(c, c->maskcc_io_dev, off + (size_t)R.g.voxels, "hipMalloc(maskcc staging)", kMccIdle))
-        return rc2;
-    char *io = static_cast<char *>(c->maskcc_io_dev.p);
-    HIP_TRY(c, hipMemcpy(io, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    vr_mask_select_info S;
-    if (int rc2 = R.select(req, io, elem_bytes, io + off, &S)) return rc2;
-    HIP_TRY(c, hipMemcpy(out_host, io + off, (size_t)R.g.voxels, hipMemcpyDeviceToHost), "hipMemcpy(selected mask)");
-    *info = S;
-    return VR_OK;
 }
 
 // Debug hook beside vr_debug.h's vr_debug_label_pass_ms (declared in no public header; tools/
@@ -309,11 +292,6 @@ int vr_debug_maskcc_pass_ms(const vr_ctx *c, float ms[9])
     return VR_OK;
 }
 
-const char *vr_maskcc_last_kernel_name(const vr_ctx *c)
-{
-    if (!c) return "";
-    if (is_group(c)) return vr_maskcc_last_kernel_name(c->members[0]);
-    return c->maskcc_last_name;
-}
+const char *vr_maskcc_last_kernel_name(const vr_ctx *c) { return mask_last_kernel_name(c, &vr_ctx::maskcc_last_name); }
 
 }  // extern "C"

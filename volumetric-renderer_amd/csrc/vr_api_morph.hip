@@ -1,13 +1,12 @@
 // vr_api_morph.hip — the exact distance transform of a mask and ball morphology (include/vr/
-// vr_morph.h) on the host scaffold of vr_ctx.h.  Built into lib/libvr_amd_morph.so, which takes
+// vr_morph.h) on the host scaffold of vr_ctx.h and vr_mask_call.h.  Built into lib/libvr_amd_morph.so, which takes
 // the scaffold (fail, hip_fail, reserve, pooled_event, the group's wait) from libvr_amd.so.
-#include "vr_ctx.h"
+#include "vr_mask_call.h"
 #include "../../include/vr/vr_morph.h"
 #include "vr_morph_kernels.h"
 
 namespace {
-static_assert(VR_EDT_NONE == kMorphNone && VR_MORPH_MAX_EXTENT == kMorphMaxExtent && VR_EINVAL == kMorphEinval &&
-                  VR_ENOSPC == kMorphEnospc && VR_OK == kMorphOk && VR_MORPH_CLOSE + 1 == kMorphOps &&
+static_assert(VR_EDT_NONE == kMorphNone && VR_MORPH_MAX_EXTENT == kMaskMaxExtent && VR_MORPH_CLOSE + 1 == kMorphOps &&
                   VR_EDT_TO_UNSET + 1 == kMorphTargets && sizeof(vr_edt_info) == 24 && sizeof(vr_morph_info) == 24,
               "vr_morph.h");
 
@@ -20,7 +19,7 @@ constexpr size_t kMorphCntBytes = 8 * sizeof(unsigned long long);  // two transf
 struct MorphRun {
     vr_ctx *c;
     hipStream_t s;
-    MorphGrid g;
+    MaskGrid g;
     Interval timed;
     int runs = 0;  // transforms so far: transform r counts into words 4 r ..
 
@@ -105,8 +104,6 @@ struct MorphRun {
     }
 };
 
-// The host forms' device copies: the mask at the block's start, the result behind it, 4-byte aligned.
-size_t io_result_offset(const MorphGrid &g, uint32_t elem_bytes) { return ((size_t)g.voxels * elem_bytes + 3) & ~(size_t)3; }
 }  // namespace
 
 extern "C" {
@@ -114,100 +111,72 @@ extern "C" {
 int vr_edt_squared_device(vr_ctx *c, const uint32_t ext[3], const void *mask_dev, uint32_t elem_bytes,
                           uint32_t target, void *dist2_dev, uint64_t dcap, vr_edt_info *info, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MorphRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = morph_check_edt(ext, mask_dev, elem_bytes, target, dist2_dev, dcap, info, true, &R.g, &msg);
-    if (rc == VR_ENOSPC) {
-        *info = vr_edt_info{R.g.voxels};  // known on the host: the voxels alone, every other field 0
-    }
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return morph_check_edt(ext, mask_dev, elem_bytes, target, dist2_dev, dcap, info, true, &R.g, msg);
+        },
+        [&](vr_ctx *m) {
             return vr_edt_squared_device(m, ext, mask_dev, elem_bytes, target, dist2_dev, dcap, info, stream);
-        });
-    vr_edt_info I;
-    if (int rc2 = R.edt(mask_dev, elem_bytes, target, dist2_dev, &I)) return rc2;
-    *info = I;
-    return VR_OK;
+        },
+        nullptr, [&](vr_edt_info *I) { return R.edt(mask_dev, elem_bytes, target, dist2_dev, I); });
 }
 
 int vr_edt_squared(vr_ctx *c, const uint32_t ext[3], const void *mask_host, uint32_t elem_bytes, uint32_t target,
                    uint32_t *dist2_host, uint64_t dcap, vr_edt_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MorphRun R{c, nullptr};
-    const char *msg;
-    const int rc = morph_check_edt(ext, mask_host, elem_bytes, target, dist2_host, dcap, info, false, &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_edt_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_edt_squared(m, ext, mask_host, elem_bytes, target, dist2_host, dcap, info);
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return morph_check_edt(ext, mask_host, elem_bytes, target, dist2_host, dcap, info, false, &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_edt_squared(m, ext, mask_host, elem_bytes, target, dist2_host, dcap, info); }, nullptr,
+        [&](vr_edt_info *I) {
+            MaskStage S{c};
+            if (int rc = S.begin(c->morph_io_dev, "hipMalloc(morph staging)", kMorphIdle,
+                                 {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {},
+                                 (size_t)R.g.voxels * 4))
+                return rc;
+            if (int rc = R.edt(S.in[0], elem_bytes, target, S.out, I)) return rc;
+            return S.finish(dist2_host, "hipMemcpy(dist2)");
         });
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t in_bytes = (size_t)R.g.voxels * elem_bytes, off = io_result_offset(R.g, elem_bytes);
-    if (int rc2 = reserve(c, c->morph_io_dev, off + (size_t)R.g.voxels * 4, "hipMalloc(morph staging)", kMorphIdle))
-        return rc2;
-    char *io = static_cast<char *>(c->morph_io_dev.p);
-    HIP_TRY(c, hipMemcpy(io, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    vr_edt_info I;
-    if (int rc2 = R.edt(io, elem_bytes, target, io + off, &I)) return rc2;
-    HIP_TRY(c, hipMemcpy(dist2_host, io + off, (size_t)R.g.voxels * 4, hipMemcpyDeviceToHost), "hipMemcpy(dist2)");
-    *info = I;
-    return VR_OK;
 }
 
 int vr_mask_morph_device(vr_ctx *c, const uint32_t ext[3], uint32_t op, uint32_t r2, const void *mask_dev,
                          uint32_t elem_bytes, void *out_dev, uint64_t mcap, vr_morph_info *info, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MorphRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = morph_check_morph(ext, op, r2, mask_dev, elem_bytes, out_dev, mcap, info, true, &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_morph_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_mask_morph_device(m, ext, op, r2, mask_dev, elem_bytes, out_dev, mcap, info, stream);
-        });
-    vr_morph_info I;
-    if (int rc2 = R.morph(op, r2, mask_dev, elem_bytes, out_dev, &I)) return rc2;
-    *info = I;
-    return VR_OK;
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return morph_check_morph(ext, op, r2, mask_dev, elem_bytes, out_dev, mcap, info, true, &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_mask_morph_device(m, ext, op, r2, mask_dev, elem_bytes, out_dev, mcap, info, stream); },
+        nullptr, [&](vr_morph_info *I) { return R.morph(op, r2, mask_dev, elem_bytes, out_dev, I); });
 }
 
 int vr_mask_morph(vr_ctx *c, const uint32_t ext[3], uint32_t op, uint32_t r2, const void *mask_host,
                   uint32_t elem_bytes, uint8_t *out_host, uint64_t mcap, vr_morph_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MorphRun R{c, nullptr};
-    const char *msg;
-    const int rc = morph_check_morph(ext, op, r2, mask_host, elem_bytes, out_host, mcap, info, false, &R.g, &msg);
-    if (rc == VR_ENOSPC) *info = vr_morph_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_mask_morph(m, ext, op, r2, mask_host, elem_bytes, out_host, mcap, info);
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return morph_check_morph(ext, op, r2, mask_host, elem_bytes, out_host, mcap, info, false, &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_mask_morph(m, ext, op, r2, mask_host, elem_bytes, out_host, mcap, info); }, nullptr,
+        [&](vr_morph_info *I) {
+            MaskStage S{c};
+            if (int rc = S.begin(c->morph_io_dev, "hipMalloc(morph staging)", kMorphIdle,
+                                 {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {}, (size_t)R.g.voxels))
+                return rc;
+            if (int rc = R.morph(op, r2, S.in[0], elem_bytes, S.out, I)) return rc;
+            return S.finish(out_host, "hipMemcpy(morph mask)");
         });
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t in_bytes = (size_t)R.g.voxels * elem_bytes, off = io_result_offset(R.g, elem_bytes);
-    if (int rc2 = reserve(c, c->morph_io_dev, off + (size_t)R.g.voxels, "hipMalloc(morph staging)", kMorphIdle))
-        return rc2;
-    char *io = static_cast<char *>(c->morph_io_dev.p);
-    HIP_TRY(c, hipMemcpy(io, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    vr_morph_info I;
-    if (int rc2 = R.morph(op, r2, io, elem_bytes, io + off, &I)) return rc2;
-    HIP_TRY(c, hipMemcpy(out_host, io + off, (size_t)R.g.voxels, hipMemcpyDeviceToHost), "hipMemcpy(morph mask)");
-    *info = I;
-    return VR_OK;
 }
 
-const char *vr_morph_last_kernel_name(const vr_ctx *c)
-{
-    if (!c) return "";
-    if (is_group(c)) return vr_morph_last_kernel_name(c->members[0]);
-    return c->morph_last_name;
-}
+const char *vr_morph_last_kernel_name(const vr_ctx *c) { return mask_last_kernel_name(c, &vr_ctx::morph_last_name); }
 
 }  // extern "C"

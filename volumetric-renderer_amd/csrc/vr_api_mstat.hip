@@ -1,14 +1,14 @@
 // vr_api_mstat.hip — the statistics of the volume under a mask or a label array and the
-// value-window pass (include/vr/vr_mstat.h) on the host scaffold of vr_ctx.h.  Built into
+// value-window pass (include/vr/vr_mstat.h) on the host scaffold of vr_ctx.h and vr_mask_call.h.  Built into
 // lib/libvr_amd_mstat.so, which takes the scaffold (fail, hip_fail, reserve, pooled_event, the
 // group's wait) from libvr_amd.so.
-#include "vr_ctx.h"
+#include "vr_mask_call.h"
 #include "../../include/vr/vr_mstat.h"
 #include "vr_mstat_kernels.h"
 
 namespace {
-static_assert(VR_MSTAT_MAX_EXTENT == kMstatMaxExtent && VR_MSTAT_NONE == kMstatNone && VR_EINVAL == kMstatEinval &&
-                  VR_ENOSPC == kMstatEnospc && VR_OK == kMstatOk && sizeof(vr_mstat_region) == kMstatRecordBytes &&
+static_assert(VR_MSTAT_MAX_EXTENT == kMaskMaxExtent && VR_MSTAT_NONE == kMstatNone &&
+                  sizeof(vr_mstat_region) == kMstatRecordBytes &&
                   sizeof(vr_label_component) == kMstatRecordBytes && sizeof(vr_mstat_info) == 32 &&
                   sizeof(vr_morph_info) == 24 && VR_HIST_MAX_BINS == kHistMaxBins,
               "vr_mstat.h");
@@ -21,7 +21,7 @@ constexpr const char *kMstatIdle = "hipDeviceSynchronize (mstat scratch)";
 struct MstatRun {
     vr_ctx *c;
     hipStream_t s;
-    MstatGrid g;
+    MaskGrid g;
     MstatArgs A;
     MstatGeom G;
     Interval timed;
@@ -167,16 +167,16 @@ struct MstatRun {
     }
 };
 
-size_t align8(size_t n) { return (n + 7) & ~(size_t)7; }
 }  // namespace
 
 extern "C" {
 
+// vr_mask_stats*: no info struct and no VR_ENOSPC, so written out on the pieces mask_call is made of.
 int vr_mask_stats_device(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], const void *mask_dev,
                          uint32_t elem_bytes, const vr_hist_request *hist, uint64_t *bins_host, vr_hist_info *hinfo,
                          vr_mstat_region *region_out, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
+    if (!c) return null_ctx();
     MstatRun R{c, static_cast<hipStream_t>(stream)};
     const char *msg;
     if (int rc = mstat_check_stats(ext, origin, mask_dev, elem_bytes, hist != nullptr, hist ? hist->use_box : 0u,
@@ -195,7 +195,7 @@ int vr_mask_stats(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], co
                   uint32_t elem_bytes, const vr_hist_request *hist, uint64_t *bins_host, vr_hist_info *hinfo,
                   vr_mstat_region *region_out)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
+    if (!c) return null_ctx();
     MstatRun R{c, nullptr};
     const char *msg;
     if (int rc = mstat_check_stats(ext, origin, mask_host, elem_bytes, hist != nullptr, hist ? hist->use_box : 0u,
@@ -207,121 +207,97 @@ int vr_mask_stats(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], co
             return vr_mask_stats(m, ext, origin, mask_host, elem_bytes, hist, bins_host, hinfo, region_out);
         });
     if (int rc = R.admit()) return rc;
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t in_bytes = (size_t)R.g.voxels * elem_bytes;
-    if (int rc = reserve(c, c->mstat_io_dev, in_bytes, "hipMalloc(mstat staging)", kMstatIdle)) return rc;
-    HIP_TRY(c, hipMemcpy(c->mstat_io_dev.p, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    return R.stats(c->mstat_io_dev.p, elem_bytes, hist, bins_host, hinfo, region_out);
+    MaskStage S{c};
+    if (int rc = S.begin(c->mstat_io_dev, "hipMalloc(mstat staging)", kMstatIdle,
+                         {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {}, 0))
+        return rc;
+    return R.stats(S.in[0], elem_bytes, hist, bins_host, hinfo, region_out);
 }
 
 int vr_label_stats_device(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], const void *labels_dev,
                           const void *table_dev, uint64_t ntable, void *regions_dev, uint64_t rcap,
                           vr_mstat_info *info, void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MstatRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = mstat_check_labels(ext, origin, labels_dev, table_dev, ntable, regions_dev, rcap, info, true, &R.g, &msg);
-    if (rc == VR_EINVAL) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mstat_check_labels(ext, origin, labels_dev, table_dev, ntable, regions_dev, rcap, info, true, &R.g, msg);
+        },
+        [&](vr_ctx *m) {
             return vr_label_stats_device(m, ext, origin, labels_dev, table_dev, ntable, regions_dev, rcap, info, stream);
-        });
-    if (int rc2 = R.admit()) return rc2;
-    if (rc == VR_ENOSPC) *info = vr_mstat_info{R.g.voxels};  // known on the host: the voxels alone, every other field 0
-    if (rc) return fail(c, rc, msg);
-    vr_mstat_info I;
-    if (int rc2 = R.labels(labels_dev, table_dev, ntable, regions_dev, &I)) return rc2;  // (waits for the stream)
-    *info = I;
-    return VR_OK;
+        },
+        [&] { return R.admit(); },
+        [&](vr_mstat_info *I) {
+            return R.labels(labels_dev, table_dev, ntable, regions_dev, I);
+        });  // (waits for the stream)
 }
 
 int vr_label_stats(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], const uint32_t *labels_host,
                    const vr_label_component *table_host, uint64_t ntable, vr_mstat_region *regions_host,
                    uint64_t rcap, vr_mstat_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MstatRun R{c, nullptr};
-    const char *msg;
-    const int rc = mstat_check_labels(ext, origin, labels_host, table_host, ntable, regions_host, rcap, info, false, &R.g,
-                                      &msg);
-    if (rc == VR_EINVAL) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_label_stats(m, ext, origin, labels_host, table_host, ntable, regions_host, rcap, info);
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mstat_check_labels(ext, origin, labels_host, table_host, ntable, regions_host, rcap, info, false,
+                                      &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_label_stats(m, ext, origin, labels_host, table_host, ntable, regions_host, rcap, info); },
+        [&] { return R.admit(); },
+        [&](vr_mstat_info *I) {
+            const size_t tab_bytes = (size_t)ntable * kMstatRecordBytes;
+            MaskStage S{c};
+            if (int rc = S.begin(c->mstat_io_dev, "hipMalloc(mstat staging)", kMstatIdle,
+                                 {labels_host, (size_t)R.g.voxels * 4, "hipMemcpy(labels)"},
+                                 {table_host, tab_bytes, "hipMemcpy(table)"}, 0))
+                return rc;
+            if (int rc = R.labels(S.in[0], S.in[1], ntable, nullptr, I)) return rc;
+            if (ntable)
+                HIP_TRY(c, hipMemcpy(regions_host, R.A.rec, tab_bytes, hipMemcpyDeviceToHost), "hipMemcpy(mstat regions)");
+            return VR_OK;
         });
-    if (int rc2 = R.admit()) return rc2;
-    if (rc == VR_ENOSPC) *info = vr_mstat_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    const size_t lab_bytes = (size_t)R.g.voxels * 4, tab_bytes = (size_t)ntable * kMstatRecordBytes;
-    if (int rc2 = reserve(c, c->mstat_io_dev, align8(lab_bytes) + tab_bytes, "hipMalloc(mstat staging)", kMstatIdle))
-        return rc2;
-    char *io = static_cast<char *>(c->mstat_io_dev.p);
-    HIP_TRY(c, hipMemcpy(io, labels_host, lab_bytes, hipMemcpyHostToDevice), "hipMemcpy(labels)");
-    if (ntable) HIP_TRY(c, hipMemcpy(io + align8(lab_bytes), table_host, tab_bytes, hipMemcpyHostToDevice), "hipMemcpy(table)");
-    vr_mstat_info I;
-    if (int rc2 = R.labels(io, io + align8(lab_bytes), ntable, nullptr, &I)) return rc2;
-    if (ntable) HIP_TRY(c, hipMemcpy(regions_host, R.A.rec, tab_bytes, hipMemcpyDeviceToHost), "hipMemcpy(mstat regions)");
-    *info = I;
-    return VR_OK;
 }
 
 int vr_mask_window_device(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], const void *mask_dev,
                           uint32_t elem_bytes, float lo, float hi, void *out_dev, uint64_t mcap, vr_morph_info *info,
                           void *stream)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MstatRun R{c, static_cast<hipStream_t>(stream)};
-    const char *msg;
-    const int rc = mstat_check_window(ext, origin, mask_dev, elem_bytes, lo, hi, out_dev, mcap, info, true, &R.g, &msg);
-    if (rc == VR_EINVAL) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mstat_check_window(ext, origin, mask_dev, elem_bytes, lo, hi, out_dev, mcap, info, true, &R.g, msg);
+        },
+        [&](vr_ctx *m) {
             return vr_mask_window_device(m, ext, origin, mask_dev, elem_bytes, lo, hi, out_dev, mcap, info, stream);
-        });
-    if (int rc2 = R.admit()) return rc2;
-    if (rc == VR_ENOSPC) *info = vr_morph_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    vr_morph_info I;
-    if (int rc2 = R.window(mask_dev, elem_bytes, lo, hi, out_dev, &I)) return rc2;
-    *info = I;
-    return VR_OK;
+        },
+        [&] { return R.admit(); },
+        [&](vr_morph_info *I) { return R.window(mask_dev, elem_bytes, lo, hi, out_dev, I); });
 }
 
 int vr_mask_window(vr_ctx *c, const uint32_t ext[3], const uint32_t origin[3], const void *mask_host,
                    uint32_t elem_bytes, float lo, float hi, uint8_t *out_host, uint64_t mcap, vr_morph_info *info)
 {
-    if (!c) return fail(nullptr, VR_EINVAL, "ctx is NULL");
     MstatRun R{c, nullptr};
-    const char *msg;
-    const int rc = mstat_check_window(ext, origin, mask_host, elem_bytes, lo, hi, out_host, mcap, info, false, &R.g, &msg);
-    if (rc == VR_EINVAL) return fail(c, rc, msg);
-    if (is_group(c))
-        return on_replica(c, [&](vr_ctx *m) {
-            return vr_mask_window(m, ext, origin, mask_host, elem_bytes, lo, hi, out_host, mcap, info);
+    return mask_call(
+        c, R.g, info,
+        [&](const char **msg) {
+            return mstat_check_window(ext, origin, mask_host, elem_bytes, lo, hi, out_host, mcap, info, false, &R.g, msg);
+        },
+        [&](vr_ctx *m) { return vr_mask_window(m, ext, origin, mask_host, elem_bytes, lo, hi, out_host, mcap, info); },
+        [&] { return R.admit(); },
+        [&](vr_morph_info *I) {
+            MaskStage S{c};  // (no mask: S.in[0] stays NULL)
+            if (int rc = S.begin(c->mstat_io_dev, "hipMalloc(mstat staging)", kMstatIdle,
+                                 {mask_host, (size_t)R.g.voxels * elem_bytes, "hipMemcpy(mask)"}, {}, (size_t)R.g.voxels))
+                return rc;
+            if (int rc = R.window(S.in[0], elem_bytes, lo, hi, S.out, I)) return rc;
+            return S.finish(out_host, "hipMemcpy(window mask)");
         });
-    if (int rc2 = R.admit()) return rc2;
-    if (rc == VR_ENOSPC) *info = vr_morph_info{R.g.voxels};
-    if (rc) return fail(c, rc, msg);
-    HIP_TRY(c, hipSetDevice(c->device), "hipSetDevice");
-    // the mask at the block's start (4-byte aligned), the result behind it
-    const size_t in_bytes = mask_host ? (size_t)R.g.voxels * elem_bytes : 0, off = align8(in_bytes);
-    if (int rc2 = reserve(c, c->mstat_io_dev, off + (size_t)R.g.voxels, "hipMalloc(mstat staging)", kMstatIdle)) return rc2;
-    char *io = static_cast<char *>(c->mstat_io_dev.p);
-    if (mask_host) HIP_TRY(c, hipMemcpy(io, mask_host, in_bytes, hipMemcpyHostToDevice), "hipMemcpy(mask)");
-    vr_morph_info I;
-    if (int rc2 = R.window(mask_host ? io : nullptr, elem_bytes, lo, hi, io + off, &I)) return rc2;
-    HIP_TRY(c, hipMemcpy(out_host, io + off, (size_t)R.g.voxels, hipMemcpyDeviceToHost), "hipMemcpy(window mask)");
-    *info = I;
-    return VR_OK;
 }
 
-const char *vr_mstat_last_kernel_name(const vr_ctx *c)
-{
-    if (!c) return "";
-    if (is_group(c)) return vr_mstat_last_kernel_name(c->members[0]);
-    return c->mstat_last_name;
-}
+const char *vr_mstat_last_kernel_name(const vr_ctx *c) { return mask_last_kernel_name(c, &vr_ctx::mstat_last_name); }
 
 }  // extern "C"

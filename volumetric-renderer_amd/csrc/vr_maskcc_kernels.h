@@ -53,7 +53,7 @@ enum MccPass {
 
 // One pass on `stream`; *name: the kernel it launched.  hipErrorInvalidValue for arguments the
 // pass cannot run on, before any launch.
-hipError_t launch_mcc(MccPass pass, const MccArgs &a, const MccGrid &g, uint32_t connectivity, hipStream_t stream,
+hipError_t launch_mcc(MccPass pass, const MccArgs &a, const MaskGrid &g, uint32_t connectivity, hipStream_t stream,
                       const char **name);
 
 }  // namespace vr

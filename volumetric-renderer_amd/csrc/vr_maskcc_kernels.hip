@@ -481,12 +481,12 @@ __global__ __launch_bounds__(256) void mcc_select_kernel(const MccArgs A)
     if ((threadIdx.x & 63u) == 0 && sum) atomicAdd(&A.cnt[kMccCntOnes], sum);
 }
 
-bool args_ok(const MccArgs &a, const MccGrid &g, const MccGeom &G)
+bool args_ok(const MccArgs &a, const MaskGrid &g, const MccGeom &G)
 {
     if (!a.P || !a.bits || !a.wpre || !a.chunk || !a.cnt || (reinterpret_cast<uintptr_t>(a.P) & 3u)) return false;
     for (int i = 0; i < 3; ++i)
-        if (a.ext[i] != g.ext[i] || g.ext[i] < 1 || g.ext[i] > kMccMaxExtent) return false;
-    if (g.voxels != (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] || g.voxels > kMccMaxVoxels) return false;
+        if (a.ext[i] != g.ext[i] || g.ext[i] < 1 || g.ext[i] > kMaskMaxExtent) return false;
+    if (g.voxels != (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] || g.voxels > kMaskMaxVoxels) return false;
     return a.nvox == (uint32_t)g.voxels && a.nwords == G.nwords && a.nchunks == G.nchunks;
 }
 
@@ -498,7 +498,7 @@ uint32_t record_grid(uint32_t ncomps)
 
 }  // namespace
 
-hipError_t launch_mcc(MccPass pass, const MccArgs &a, const MccGrid &g, uint32_t connectivity, hipStream_t stream,
+hipError_t launch_mcc(MccPass pass, const MccArgs &a, const MaskGrid &g, uint32_t connectivity, hipStream_t stream,
                       const char **name)
 {
     const MccGeom G = mcc_geometry(g);

@@ -30,9 +30,9 @@ struct MorphArgs {
 
 // Pass 1, along x: dist[l] = the squared distance to the nearest target voxel of l's row (kMorphNone
 // without one, or above limit); cnt[0] += the mask's set voxels.
-hipError_t launch_morph_edt_x(const MorphArgs &a, const MorphGrid &g, hipStream_t stream, const char **name);
+hipError_t launch_morph_edt_x(const MorphArgs &a, const MaskGrid &g, hipStream_t stream, const char **name);
 // Passes 2 and 3, along axis 1 (y) or 2 (z): the lower envelope of the columns, in place.
-hipError_t launch_morph_edt_axis(const MorphArgs &a, const MorphGrid &g, int axis, MorphFinal fin,
+hipError_t launch_morph_edt_axis(const MorphArgs &a, const MaskGrid &g, int axis, MorphFinal fin,
                                  hipStream_t stream, const char **name);
 
 }  // namespace vr

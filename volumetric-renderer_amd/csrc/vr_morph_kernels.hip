@@ -14,7 +14,7 @@ namespace vr {
 namespace {
 
 constexpr uint32_t kXWaves = 4;                       // rows a workgroup walks at a time, a wave each
-constexpr uint32_t kXWords = kMorphMaxExtent / 64u;   // 64-voxel words of the longest row
+constexpr uint32_t kXWords = kMaskMaxExtent / 64u;    // 64-voxel words of the longest row
 constexpr uint32_t kAxisThreads = 512;
 constexpr uint32_t kMaxGrid = 8192;                   // workgroups of a launch: the rest is strided
 
@@ -236,17 +236,17 @@ hipError_t launch_axis(const MorphArgs &a, const MorphAxis &X, hipStream_t strea
     return hipGetLastError();
 }
 
-bool args_ok(const MorphArgs &a, const MorphGrid &g)
+bool args_ok(const MorphArgs &a, const MaskGrid &g)
 {
     if (!a.dist || !a.cnt || (reinterpret_cast<uintptr_t>(a.dist) & 3u)) return false;
     for (int i = 0; i < 3; ++i)
-        if (a.ext[i] != g.ext[i] || g.ext[i] < 1 || g.ext[i] > kMorphMaxExtent) return false;
-    return g.voxels == (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] && g.voxels <= kMorphMaxVoxels;
+        if (a.ext[i] != g.ext[i] || g.ext[i] < 1 || g.ext[i] > kMaskMaxExtent) return false;
+    return g.voxels == (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] && g.voxels <= kMaskMaxVoxels;
 }
 
 }  // namespace
 
-hipError_t launch_morph_edt_x(const MorphArgs &a, const MorphGrid &g, hipStream_t stream, const char **name)
+hipError_t launch_morph_edt_x(const MorphArgs &a, const MaskGrid &g, hipStream_t stream, const char **name)
 {
     if (!args_ok(a, g) || !a.mask || (a.elem_bytes != 1 && a.elem_bytes != 4)) return hipErrorInvalidValue;
     const uint64_t nrows = (uint64_t)g.ext[1] * g.ext[2];
@@ -262,7 +262,7 @@ hipError_t launch_morph_edt_x(const MorphArgs &a, const MorphGrid &g, hipStream_
     return hipGetLastError();
 }
 
-hipError_t launch_morph_edt_axis(const MorphArgs &a, const MorphGrid &g, int axis, MorphFinal fin,
+hipError_t launch_morph_edt_axis(const MorphArgs &a, const MaskGrid &g, int axis, MorphFinal fin,
                                  hipStream_t stream, const char **name)
 {
     if (!args_ok(a, g) || (axis != 1 && axis != 2) || (fin == kMorphThresh && !a.out)) return hipErrorInvalidValue;

@@ -1,6 +1,7 @@
-// vr_mstat_host.h — the host side of include/vr/vr_mstat.h: what a request is refused for, the grid
-// it resolves to, the launch geometry and scratch layout of its passes, and the voxel-to-element
-// addressing of the base bricks, which the kernels share.  Plain C++ without HIP, so a stand-alone
+// vr_mstat_host.h — the host side of include/vr/vr_mstat.h: what a request is refused for (the grid
+// rule is vr_mask_host.h's, the texts, the origin and the request's own fields are here), the launch
+// geometry and scratch layout of its passes, and the voxel-to-element addressing of the base
+// bricks, which the kernels share.  Plain C++ without HIP, so a stand-alone
 // program can run it (under a sanitizer, tests/test_mstat_cpu.py); vr_api_mstat.hip includes it for
 // the entry points, vr_mstat_kernels.hip for the geometry and the addressing.
 #pragma once
@@ -11,6 +12,7 @@
 #include <cmath>
 
 #include "vr_hist_host.h"  // hist_range_ok, and with it vr_box_host.h
+#include "vr_mask_host.h"
 
 #if defined(__HIPCC__)
 #define VR_MSTAT_HD __host__ __device__
@@ -20,10 +22,7 @@
 
 namespace vr {
 
-constexpr uint32_t kMstatMaxExtent = 32768u;         // VR_MSTAT_MAX_EXTENT
-constexpr uint64_t kMstatMaxVoxels = 0xFFFFFFFFull;  // a box-linear index is 32 bits
-constexpr uint64_t kMstatMaxTable = 0xFFFFFFFFull;   // and so is a record slot
-constexpr int kMstatOk = 0, kMstatEinval = -22, kMstatEnospc = -28;  // VR_OK, VR_EINVAL, VR_ENOSPC
+constexpr uint64_t kMstatMaxTable = 0xFFFFFFFFull;   // a record slot is 32 bits, as a box-linear index
 constexpr uint32_t kMstatNone = 0xFFFFFFFFu;         // VR_MSTAT_NONE
 constexpr uint32_t kMstatRecordBytes = 64;           // sizeof(vr_mstat_region), sizeof(vr_label_component)
 constexpr uint32_t kMstatAccBytes = 48;              // one region's accumulators (vr_mstat_kernels.h MstatAcc)
@@ -66,57 +65,24 @@ VR_MSTAT_HD constexpr uint64_t mstat_element(const MstatLayout &L, uint32_t nbx,
 }
 
 // ---- the grid ----
-struct MstatGrid {
-    uint32_t ext[3];
-    uint32_t origin[3];
-    uint64_t voxels;
-};
+// The family's texts for the shared rule (vr_mask_host.h MaskReason; the outputs' are below).
+constexpr const char *kMstatTexts[kMaskAlign + 1] = {
+    nullptr, "grid extent must lie in [1, 32768]", "grid holds more than 2^32 - 1 voxels", "elem_bytes must be 1 or 4",
+    "a 4-byte array must be 4-byte aligned"};
 
-// The grid of ext into *g; nullptr, or what is wrong (*g is then untouched).  vr_morph.h's rule.
-inline const char *mstat_grid_resolve(const uint32_t ext[3], MstatGrid *g)
-{
-    uint64_t n = 1;
-    for (int a = 0; a < 3; ++a) {
-        if (ext[a] < 1 || ext[a] > kMstatMaxExtent) return "grid extent must lie in [1, 32768]";
-        n *= ext[a];  // (at most 2^45)
-    }
-    if (n > kMstatMaxVoxels) return "grid holds more than 2^32 - 1 voxels";
-    for (int a = 0; a < 3; ++a) g->ext[a] = ext[a];
-    g->voxels = n;
-    return nullptr;
-}
-
-// [a, a + na) and [b, b + nb) share a byte.
-inline bool mstat_overlap(const void *a, uint64_t na, const void *b, uint64_t nb)
-{
-    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
-    return pa < pb ? pb - pa < na : pa - pb < nb;
-}
-
-inline bool mstat_aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
-// A refusal: its text into *msg, its code returned.
-inline int mstat_refuse(const char **msg, const char *text, int code)
-{
-    *msg = text;
-    return code;
-}
-
-// What every call shares: the extents, the origin's presence, the element width and the array's
-// alignment (device memory only: a host array is copied byte by byte).
+// What every call shares: the extents, the origin, the element width and the array's alignment
+// (array may be NULL where the call allows it).
 inline int mstat_check_grid(const uint32_t *ext, const uint32_t *origin, const void *array, uint32_t elem_bytes,
-                            bool device, MstatGrid *r, const char **msg)
+                            bool device, MaskGrid *r, const char **msg)
 {
-    if (const char *m = mstat_grid_resolve(ext, r)) return mstat_refuse(msg, m, kMstatEinval);
+    if (MaskReason why = mask_grid_resolve(ext, r)) return mask_refuse(msg, kMstatTexts[why], kMaskEinval);
     for (int a = 0; a < 3; ++a) r->origin[a] = origin[a];
-    if (elem_bytes != 1 && elem_bytes != 4) return mstat_refuse(msg, "elem_bytes must be 1 or 4", kMstatEinval);
-    if (device && elem_bytes == 4 && array && !mstat_aligned4(array))
-        return mstat_refuse(msg, "a 4-byte array must be 4-byte aligned", kMstatEinval);
-    return kMstatOk;
+    if (MaskReason why = mask_check_array(array, elem_bytes, device)) return mask_refuse(msg, kMstatTexts[why], kMaskEinval);
+    return kMaskOk;
 }
 
 // The grid against the volume (after the context lookup): origin[a] + ext[a] <= dims[a].
-inline const char *mstat_origin_error(const MstatGrid &g, const uint32_t dims[3])
+inline const char *mstat_origin_error(const MaskGrid &g, const uint32_t dims[3])
 {
     constexpr const char *text = "origin + ext lies beyond the volume";
     uint32_t hi[3];
@@ -128,67 +94,59 @@ inline const char *mstat_origin_error(const MstatGrid &g, const uint32_t dims[3]
     return box_resolve(1, g.origin, hi, dims, &b) == kBoxOk ? nullptr : text;
 }
 
-// vr_mask_stats*: kMstatOk with *g resolved, or kMstatEinval (*g untouched).  have_hist: the request
+// vr_mask_stats*: kMaskOk with *g resolved, or kMaskEinval (*g untouched).  have_hist: the request
 // is not NULL, and then (use_box, lo, hi, nbins) are its fields.
 inline int mstat_check_stats(const uint32_t *ext, const uint32_t *origin, const void *mask, uint32_t elem_bytes,
                              bool have_hist, uint32_t use_box, float lo, float hi, uint32_t nbins, const void *bins,
-                             const void *hinfo, const void *region, bool device, MstatGrid *g, const char **msg)
+                             const void *hinfo, const void *region, bool device, MaskGrid *g, const char **msg)
 {
     *msg = nullptr;
-    if (!ext || !origin || !mask || !region) return mstat_refuse(msg, "NULL argument", kMstatEinval);
+    if (!ext || !origin || !mask || !region) return mask_refuse(msg, "NULL argument", kMaskEinval);
     if (have_hist ? (!bins || !hinfo) : (bins || hinfo))
-        return mstat_refuse(msg, "bins and hinfo are NULL exactly when the histogram request is", kMstatEinval);
-    MstatGrid r;
+        return mask_refuse(msg, "bins and hinfo are NULL exactly when the histogram request is", kMaskEinval);
+    MaskGrid r;
     if (int rc = mstat_check_grid(ext, origin, mask, elem_bytes, device, &r, msg)) return rc;
     if (have_hist) {
-        if (use_box != 0) return mstat_refuse(msg, "a mask histogram takes no box: use_box must be 0", kMstatEinval);
+        if (use_box != 0) return mask_refuse(msg, "a mask histogram takes no box: use_box must be 0", kMaskEinval);
         if (!hist_range_ok(lo, hi, nbins))
-            return mstat_refuse(msg, "histogram needs finite lo < hi and 1 <= nbins <= 4096", kMstatEinval);
+            return mask_refuse(msg, "histogram needs finite lo < hi and 1 <= nbins <= 4096", kMaskEinval);
     }
     *g = r;
-    return kMstatOk;
+    return kMaskOk;
 }
 
-// vr_label_stats*: kMstatOk, kMstatEinval (*g untouched), or kMstatEnospc for rcap below ntable with
-// *g resolved (the caller reports g->voxels).  The overlap is that of what a full-size call touches.
+// vr_label_stats*: kMaskOk, kMaskEinval (*g untouched), or kMaskEnospc for rcap below ntable with
+// *g resolved (the caller reports g->voxels).  A full-size call writes ntable records.
 inline int mstat_check_labels(const uint32_t *ext, const uint32_t *origin, const void *labels, const void *table,
                               uint64_t ntable, const void *regions, uint64_t rcap, const void *info, bool device,
-                              MstatGrid *g, const char **msg)
+                              MaskGrid *g, const char **msg)
 {
     *msg = nullptr;
-    if (!ext || !origin || !labels || !table || !regions || !info) return mstat_refuse(msg, "NULL argument", kMstatEinval);
-    MstatGrid r;
+    if (!ext || !origin || !labels || !table || !regions || !info) return mask_refuse(msg, "NULL argument", kMaskEinval);
+    MaskGrid r;
     if (int rc = mstat_check_grid(ext, origin, labels, 4, device, &r, msg)) return rc;
-    if (ntable > kMstatMaxTable) return mstat_refuse(msg, "the table holds more than 2^32 - 1 records", kMstatEinval);
-    const uint64_t rn = rcap < ntable ? rcap : ntable;
-    if (rn && mstat_overlap(labels, r.voxels * 4, regions, rn * kMstatRecordBytes))
-        return mstat_refuse(msg, "the region buffer overlaps the labels", kMstatEinval);
-    if (rn && mstat_overlap(table, ntable * kMstatRecordBytes, regions, rn * kMstatRecordBytes))
-        return mstat_refuse(msg, "the region buffer overlaps the table", kMstatEinval);
-    *g = r;
-    if (rcap < ntable)
-        return mstat_refuse(msg, "the region buffer is smaller than the table (see the info's regions)", kMstatEnospc);
-    return kMstatOk;
+    if (ntable > kMstatMaxTable) return mask_refuse(msg, "the table holds more than 2^32 - 1 records", kMaskEinval);
+    if (mask_check_output(labels, r.voxels * 4, regions, kMstatRecordBytes, rcap, ntable) == kMaskOverlap)
+        return mask_refuse(msg, "the region buffer overlaps the labels", kMaskEinval);
+    const MaskReason o = mask_check_output(table, ntable * kMstatRecordBytes, regions, kMstatRecordBytes, rcap, ntable);
+    if (o == kMaskOverlap) return mask_refuse(msg, "the region buffer overlaps the table", kMaskEinval);
+    return mask_resolved(r, o, "the region buffer is smaller than the table (see the info's regions)", g, msg);
 }
 
 // vr_mask_window*: the same for the byte output and the window (vr_label.h's); mask may be NULL.
 inline int mstat_check_window(const uint32_t *ext, const uint32_t *origin, const void *mask, uint32_t elem_bytes,
                               float lo, float hi, const void *out, uint64_t mcap, const void *info, bool device,
-                              MstatGrid *g, const char **msg)
+                              MaskGrid *g, const char **msg)
 {
     *msg = nullptr;
-    if (!ext || !origin || !out || !info) return mstat_refuse(msg, "NULL argument", kMstatEinval);
-    MstatGrid r;
+    if (!ext || !origin || !out || !info) return mask_refuse(msg, "NULL argument", kMaskEinval);
+    MaskGrid r;
     if (int rc = mstat_check_grid(ext, origin, mask, elem_bytes, device, &r, msg)) return rc;
-    if (std::isnan(lo) || std::isnan(hi)) return mstat_refuse(msg, "window bounds must not be NaN", kMstatEinval);
-    if (lo > hi) return mstat_refuse(msg, "window needs lo <= hi", kMstatEinval);
-    const uint64_t on = mcap < r.voxels ? mcap : r.voxels;
-    if (mask && on && mstat_overlap(mask, r.voxels * elem_bytes, out, on))
-        return mstat_refuse(msg, "the output overlaps the mask", kMstatEinval);
-    *g = r;
-    if (mcap < r.voxels)
-        return mstat_refuse(msg, "the output buffer is smaller than the grid (see the info's voxels)", kMstatEnospc);
-    return kMstatOk;
+    if (std::isnan(lo) || std::isnan(hi)) return mask_refuse(msg, "window bounds must not be NaN", kMaskEinval);
+    if (lo > hi) return mask_refuse(msg, "window needs lo <= hi", kMaskEinval);
+    const MaskReason o = mask_check_output(mask, r.voxels * elem_bytes, out, 1, mcap, r.voxels);
+    if (o == kMaskOverlap) return mask_refuse(msg, "the output overlaps the mask", kMaskEinval);
+    return mask_resolved(r, o, "the output buffer is smaller than the grid (see the info's voxels)", g, msg);
 }
 
 // ---- the launch geometry and the scratch of one call (vr_mstat_kernels.hip) ----
@@ -204,7 +162,7 @@ struct MstatGeom {
     size_t cnt, bins, edges, acc, rec, lab, bytes;  // offsets into the scratch block and its size
 };
 
-inline MstatGeom mstat_geometry(const MstatGrid &g, uint64_t nrec)
+inline MstatGeom mstat_geometry(const MaskGrid &g, uint64_t nrec)
 {
     MstatGeom G;
     G.tiles_x = (g.ext[0] + kMstatTileX - 1) / kMstatTileX;

@@ -61,7 +61,7 @@ enum MstatPass {
 
 // One pass on `stream` over the base bricks of layout code `layout`; *name: the kernel it launched.
 // hipErrorInvalidValue for arguments the pass cannot run on, before any launch.
-hipError_t launch_mstat(MstatPass pass, int layout, const MstatArgs &a, const MstatGrid &g, hipStream_t stream,
+hipError_t launch_mstat(MstatPass pass, int layout, const MstatArgs &a, const MaskGrid &g, hipStream_t stream,
                         const char **name);
 
 }  // namespace vr

@@ -172,7 +172,7 @@ __device__ __forceinline__ Voxel tile_voxel(const MstatArgs &A, uint32_t t, uint
     v.j = ty * kMstatTileY + (threadIdx.x >> 6);
     v.x = tx * kMstatTileX + (threadIdx.x & 63u);
     v.in = v.x < A.ext[0] && v.j < A.ext[1];
-    v.l = v.in ? v.x + A.ext[0] * (v.j + A.ext[1] * v.k) : 0u;  // below 2^32 - 1 (mstat_grid_resolve)
+    v.l = v.in ? v.x + A.ext[0] * (v.j + A.ext[1] * v.k) : 0u;  // below 2^32 - 1 (mask_grid_resolve)
     return v;
 }
 // the array's element of voxel l is non-zero (a NULL array: every voxel is set)
@@ -484,12 +484,12 @@ __global__ __launch_bounds__(256) void mstat_window_kernel(const MstatArgs A, co
     }
 }
 
-bool args_ok(const MstatArgs &a, const MstatGrid &g)
+bool args_ok(const MstatArgs &a, const MaskGrid &g)
 {
     if (!a.cnt) return false;
     for (int i = 0; i < 3; ++i)
-        if (a.ext[i] != g.ext[i] || a.origin[i] != g.origin[i] || g.ext[i] < 1 || g.ext[i] > kMstatMaxExtent) return false;
-    return g.voxels == (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] && g.voxels <= kMstatMaxVoxels;
+        if (a.ext[i] != g.ext[i] || a.origin[i] != g.origin[i] || g.ext[i] < 1 || g.ext[i] > kMaskMaxExtent) return false;
+    return g.voxels == (uint64_t)g.ext[0] * g.ext[1] * g.ext[2] && g.voxels <= kMaskMaxVoxels;
 }
 
 // DO(T, KIND, "tag") for the kernel types of base layout code `layout`; `bad` for any other code.
@@ -507,7 +507,7 @@ bool args_ok(const MstatArgs &a, const MstatGrid &g)
 
 }  // namespace
 
-hipError_t launch_mstat(MstatPass pass, int layout, const MstatArgs &a, const MstatGrid &g, hipStream_t stream,
+hipError_t launch_mstat(MstatPass pass, int layout, const MstatArgs &a, const MaskGrid &g, hipStream_t stream,
                         const char **name)
 {
     if (!args_ok(a, g)) return hipErrorInvalidValue;

@@ -434,109 +434,80 @@ def lib() -> C.CDLL:
     return L
 
 
-MORPH_LIB_PATH = os.environ.get("VR_AMD_MORPH_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                    "libvr_amd_morph.so")
-_MORPH_LIB = None
+def _family_signatures() -> dict:
+    """family -> {entry point: (restype, argtypes)} of the libraries beside libvr_amd.so."""
+    vp, u32, u64, i32, f32, P = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_float, C.POINTER
+    ext, name = P(u32), (C.c_char_p, [vp])
+    ei, mi, li, si = P(vr_edt_info), P(vr_morph_info), P(vr_label_info), P(vr_mask_select_info)
+    req, hr, hi = P(vr_mask_select_request), P(vr_hist_request), P(vr_hist_info)
+    ti, reg = P(vr_mstat_info), P(vr_mstat_region)
+    return {
+        "morph": {
+            "vr_edt_squared_device": (i32, [vp, ext, vp, u32, u32, vp, u64, ei, vp]),
+            "vr_edt_squared": (i32, [vp, ext, vp, u32, u32, vp, u64, ei]),
+            "vr_mask_morph_device": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, mi, vp]),
+            "vr_mask_morph": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, mi]),
+            "vr_morph_last_kernel_name": name,
+        },
+        "maskcc": {
+            "vr_mask_label_device": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li, vp]),
+            "vr_mask_label": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li]),
+            "vr_mask_select_device": (i32, [vp, ext, req, vp, u32, vp, u64, si, vp]),
+            "vr_mask_select": (i32, [vp, ext, req, vp, u32, vp, u64, si]),
+            "vr_maskcc_last_kernel_name": name,
+            "vr_debug_maskcc_pass_ms": (i32, [vp, P(f32)]),  # (a debug hook, in no header)
+        },
+        "mstat": {
+            "vr_mask_stats_device": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, reg, vp]),
+            "vr_mask_stats": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, reg]),
+            "vr_label_stats_device": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, ti, vp]),
+            "vr_label_stats": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, ti]),
+            "vr_mask_window_device": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, mi, vp]),
+            "vr_mask_window": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, mi]),
+            "vr_mstat_last_kernel_name": name,
+        },
+    }
+
+
+# family -> (the environment variable that names its library, the file beside LIB_PATH otherwise)
+FAMILY_LIBS = {"morph": ("VR_AMD_MORPH_LIB", "libvr_amd_morph.so"),
+               "maskcc": ("VR_AMD_MASKCC_LIB", "libvr_amd_maskcc.so"),
+               "mstat": ("VR_AMD_MSTAT_LIB", "libvr_amd_mstat.so")}
+FAMILY_LIB_PATHS = {f: os.environ.get(env) or os.path.join(os.path.dirname(LIB_PATH), so)
+                    for f, (env, so) in FAMILY_LIBS.items()}
+MORPH_LIB_PATH, MASKCC_LIB_PATH, MSTAT_LIB_PATH = (FAMILY_LIB_PATHS[f] for f in ("morph", "maskcc", "mstat"))
+_FAMILY_LIBS = {}
+
+
+def family_lib(family: str) -> C.CDLL:
+    """Load lib/libvr_amd_<family>.so (vr_<family>.h) on first use, after lib(): it takes the host
+    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
+    if family in _FAMILY_LIBS:
+        return _FAMILY_LIBS[family]
+    lib()
+    path = FAMILY_LIB_PATHS[family]
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} is missing: build it with `make -C volumetric-renderer_amd` "
+                           "(or __graft_entry__.build()); there is no CPU fallback")
+    L = C.CDLL(path)
+    for name, (res, args) in _family_signatures()[family].items():
+        fn = getattr(L, name)
+        fn.restype = res
+        fn.argtypes = args
+    _FAMILY_LIBS[family] = L
+    return L
 
 
 def morph_lib() -> C.CDLL:
-    """Load lib/libvr_amd_morph.so (vr_morph.h) on first use, after lib(): it takes the host
-    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
-    global _MORPH_LIB
-    if _MORPH_LIB is not None:
-        return _MORPH_LIB
-    lib()
-    if not os.path.exists(MORPH_LIB_PATH):
-        raise RuntimeError(f"{MORPH_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
-                           "(or __graft_entry__.build()); there is no CPU fallback")
-    L = C.CDLL(MORPH_LIB_PATH)
-    vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-    ext = C.POINTER(u32)
-    sig = {
-        "vr_edt_squared_device": (i32, [vp, ext, vp, u32, u32, vp, u64, C.POINTER(vr_edt_info), vp]),
-        "vr_edt_squared": (i32, [vp, ext, vp, u32, u32, vp, u64, C.POINTER(vr_edt_info)]),
-        "vr_mask_morph_device": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, C.POINTER(vr_morph_info), vp]),
-        "vr_mask_morph": (i32, [vp, ext, u32, u32, vp, u32, vp, u64, C.POINTER(vr_morph_info)]),
-        "vr_morph_last_kernel_name": (C.c_char_p, [vp]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _MORPH_LIB = L
-    return L
-
-
-MASKCC_LIB_PATH = os.environ.get("VR_AMD_MASKCC_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                      "libvr_amd_maskcc.so")
-_MASKCC_LIB = None
+    return family_lib("morph")
 
 
 def maskcc_lib() -> C.CDLL:
-    """Load lib/libvr_amd_maskcc.so (vr_maskcc.h) on first use, after lib(): it takes the host
-    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
-    global _MASKCC_LIB
-    if _MASKCC_LIB is not None:
-        return _MASKCC_LIB
-    lib()
-    if not os.path.exists(MASKCC_LIB_PATH):
-        raise RuntimeError(f"{MASKCC_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
-                           "(or __graft_entry__.build()); there is no CPU fallback")
-    L = C.CDLL(MASKCC_LIB_PATH)
-    vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int
-    ext = C.POINTER(u32)
-    req, li, si = C.POINTER(vr_mask_select_request), C.POINTER(vr_label_info), C.POINTER(vr_mask_select_info)
-    sig = {
-        "vr_mask_label_device": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li, vp]),
-        "vr_mask_label": (i32, [vp, ext, vp, u32, u32, vp, u64, vp, u64, li]),
-        "vr_mask_select_device": (i32, [vp, ext, req, vp, u32, vp, u64, si, vp]),
-        "vr_mask_select": (i32, [vp, ext, req, vp, u32, vp, u64, si]),
-        "vr_maskcc_last_kernel_name": (C.c_char_p, [vp]),
-        "vr_debug_maskcc_pass_ms": (i32, [vp, C.POINTER(C.c_float)]),  # (a debug hook, in no header)
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _MASKCC_LIB = L
-    return L
-
-
-MSTAT_LIB_PATH = os.environ.get("VR_AMD_MSTAT_LIB") or os.path.join(os.path.dirname(LIB_PATH),
-                                                                    "libvr_amd_mstat.so")
-_MSTAT_LIB = None
+    return family_lib("maskcc")
 
 
 def mstat_lib() -> C.CDLL:
-    """Load lib/libvr_amd_mstat.so (vr_mstat.h) on first use, after lib(): it takes the host
-    scaffold from libvr_amd.so.  Fails loudly: there is no fallback path."""
-    global _MSTAT_LIB
-    if _MSTAT_LIB is not None:
-        return _MSTAT_LIB
-    lib()
-    if not os.path.exists(MSTAT_LIB_PATH):
-        raise RuntimeError(f"{MSTAT_LIB_PATH} is missing: build it with `make -C volumetric-renderer_amd` "
-                           "(or __graft_entry__.build()); there is no CPU fallback")
-    L = C.CDLL(MSTAT_LIB_PATH)
-    vp, u32, u64, i32, f32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_float
-    ext = C.POINTER(u32)
-    hr, hi, mi, wi = (C.POINTER(vr_hist_request), C.POINTER(vr_hist_info), C.POINTER(vr_mstat_info),
-                      C.POINTER(vr_morph_info))
-    sig = {
-        "vr_mask_stats_device": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, C.POINTER(vr_mstat_region), vp]),
-        "vr_mask_stats": (i32, [vp, ext, ext, vp, u32, hr, vp, hi, C.POINTER(vr_mstat_region)]),
-        "vr_label_stats_device": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, mi, vp]),
-        "vr_label_stats": (i32, [vp, ext, ext, vp, vp, u64, vp, u64, mi]),
-        "vr_mask_window_device": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, wi, vp]),
-        "vr_mask_window": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, wi]),
-        "vr_mstat_last_kernel_name": (C.c_char_p, [vp]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(L, name)
-        fn.restype = res
-        fn.argtypes = args
-    _MSTAT_LIB = L
-    return L
+    return family_lib("mstat")
 
 
 def mstat_region_dict(r: vr_mstat_region) -> dict:
@@ -1215,7 +1186,7 @@ class OffscreenPass:
         dict when the buffer is complete.  ext: (bx, by, bz)."""
         info = vr_edt_info()
         self._check(morph_lib().vr_edt_squared_device(
-            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.c_void_p(mask_ptr), int(elem_bytes),
+            self._ctx, self._u3(ext), C.c_void_p(mask_ptr), int(elem_bytes),
             EDT_TO_SET if to_set else EDT_TO_UNSET, C.c_void_p(dist2_ptr), int(dcap), C.byref(info),
             C.c_void_p(stream or None)), "distance_transform_device")
         return self._edt_info(info)
@@ -1236,7 +1207,7 @@ class OffscreenPass:
         dict when the buffer is complete.  ext: (bx, by, bz)."""
         info = vr_morph_info()
         self._check(morph_lib().vr_mask_morph_device(
-            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), int(op), int(r2), C.c_void_p(mask_ptr),
+            self._ctx, self._u3(ext), int(op), int(r2), C.c_void_p(mask_ptr),
             int(elem_bytes), C.c_void_p(out_ptr), int(mcap), C.byref(info), C.c_void_p(stream or None)),
             "morph_device")
         return self._morph_info(info)
@@ -1276,7 +1247,7 @@ class OffscreenPass:
         the info dict when both buffers are complete.  ext: (bx, by, bz)."""
         info = vr_label_info()
         self._check(maskcc_lib().vr_mask_label_device(
-            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.c_void_p(mask_ptr), int(elem_bytes),
+            self._ctx, self._u3(ext), C.c_void_p(mask_ptr), int(elem_bytes),
             int(connectivity), C.c_void_p(labels_ptr), int(lcap), C.c_void_p(comps_ptr), int(ccap), C.byref(info),
             C.c_void_p(stream or None)), "mask_label_device")
         return self._label_info(info)
@@ -1299,7 +1270,7 @@ class OffscreenPass:
         req = mask_select_request(rule, connectivity, min_voxels, seed)
         info = vr_mask_select_info()
         self._check(maskcc_lib().vr_mask_select_device(
-            self._ctx, (C.c_uint32 * 3)(*[int(v) for v in ext]), C.byref(req), C.c_void_p(mask_ptr),
+            self._ctx, self._u3(ext), C.byref(req), C.c_void_p(mask_ptr),
             int(elem_bytes), C.c_void_p(out_ptr), int(mcap), C.byref(info), C.c_void_p(stream or None)),
             "mask_select_device")
         return self._select_info(info)
