@@ -182,6 +182,12 @@ struct vr_ctx {
     // kernel (vr_mstat_last_kernel_name)
     DevBlock mstat_aux_dev, mstat_io_dev;
     const char *mstat_last_name = "";
+    // vr_mask_occupancy_device, vr_mask_hit_render*, vr_mask_pick, vr_mask_slice* (vr_mview.h;
+    // csrc/vr_api_mview.hip in lib/libvr_amd_mview.so): the counters of a call, and the host forms'
+    // and the pick's device copies of their array and their output; both grown on demand.
+    // mview_last_name: the family's last kernel (vr_mview_last_kernel_name)
+    DevBlock mview_cnt_dev, mview_io_dev;
+    const char *mview_last_name = "";
     // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
     // taken while timing is enabled; 0 for a pass that call did not run
     float label_pass_ms[kLabelPassSlots] = {};

@@ -1,5 +1,5 @@
 // vr_mask_host.h — the one statement of the grid rule of the mask families (include/vr/vr_morph.h,
-// vr_maskcc.h, vr_mstat.h): the grid a request resolves to, its two bounds, and what an array or an
+// vr_maskcc.h, vr_mstat.h, vr_mview.h): the grid a request resolves to, its two bounds, and what an array or an
 // output of a call is refused for.  Like vr_box_host.h it answers with a reason code; each family
 // (vr_<family>_host.h) owns the texts, its further request fields and its geometry.  Plain C++
 // without HIP, so a stand-alone program can run it (under a sanitizer, tests/test_mask_host_cpu.py).
@@ -9,7 +9,7 @@
 
 namespace vr {
 
-constexpr uint32_t kMaskMaxExtent = 32768u;         // VR_MORPH_MAX_EXTENT, VR_MASKCC_MAX_EXTENT, VR_MSTAT_MAX_EXTENT
+constexpr uint32_t kMaskMaxExtent = 32768u;         // VR_MORPH_MAX_EXTENT, VR_MASKCC_MAX_EXTENT, VR_MSTAT_MAX_EXTENT, VR_MVIEW_MAX_EXTENT
 constexpr uint64_t kMaskMaxVoxels = 0xFFFFFFFFull;  // a box-linear index, and 1 + it, fits 32 bits
 constexpr int kMaskOk = 0, kMaskEinval = -22, kMaskEnospc = -28;  // VR_OK, VR_EINVAL, VR_ENOSPC
 

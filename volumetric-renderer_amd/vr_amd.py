@@ -175,6 +175,25 @@ class vr_mstat_info(C.Structure):  # vr_mstat.h
     _fields_ = [("voxels", C.c_uint64), ("set", C.c_uint64), ("unlisted", C.c_uint64), ("regions", C.c_uint64)]
 
 
+class vr_mview_source(C.Structure):  # vr_mview.h
+    _fields_ = [("ext", C.c_uint32 * 3), ("origin", C.c_uint32 * 3), ("elem_bytes", C.c_uint32),
+                ("select", C.c_uint32), ("label", C.c_uint32), ("reserved", C.c_uint32),
+                ("array", C.c_void_p), ("occupancy", C.c_void_p)]
+
+
+class vr_mask_hit(C.Structure):  # vr_mview.h
+    _fields_ = [("pos", C.c_float * 3), ("depth", C.c_float), ("element", C.c_uint32), ("step", C.c_uint32),
+                ("index", C.c_uint32), ("normal", C.c_int8 * 3), ("reserved", C.c_uint8)]
+
+
+class vr_mview_info(C.Structure):  # vr_mview.h
+    _fields_ = [(n, C.c_uint64) for n in ("voxels", "pixels", "covered", "hits", "steps", "samples")]
+
+
+class vr_mview_occ_info(C.Structure):  # vr_mview.h
+    _fields_ = [(n, C.c_uint64) for n in ("voxels", "cells", "cells_set", "matching")]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -266,6 +285,18 @@ MSTAT_REGION_DTYPE = np.dtype([("label", "<u4"), ("reserved", "<u4"), ("voxels",
                                ("sum", "<f8"), ("sum2", "<f8"), ("reserved2", "<u8")])
 MSTAT_NONE = 0xFFFFFFFF
 MSTAT_MAX_EXTENT = 32768
+# include/vr/vr_mview.h: the view of a mask or a label array -- first-hit records, the slice's elements, the
+# pick and the occupancy words; the entry points live in a fifth library, lib/libvr_amd_mview.so
+# (mview_lib()), on the same context
+MVIEW_SYMBOLS = ["vr_mview_occupancy_words", "vr_mask_occupancy_device", "vr_mask_hit_render_device",
+                 "vr_mask_hit_render", "vr_mask_pick", "vr_mask_slice_device", "vr_mask_slice",
+                 "vr_mview_last_kernel_name"]
+MVIEW_HIT_DTYPE = np.dtype([("pos", "<f4", 3), ("depth", "<f4"), ("element", "<u4"), ("step", "<u4"),
+                            ("index", "<u4"), ("normal", "i1", 3), ("reserved", "u1")])
+MVIEW_ANY, MVIEW_LABEL = 0, 1
+MVIEW_MISS = 0xFFFFFFFF
+MVIEW_CELL = 8
+MVIEW_MAX_EXTENT = 32768
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -441,6 +472,8 @@ def _family_signatures() -> dict:
     ei, mi, li, si = P(vr_edt_info), P(vr_morph_info), P(vr_label_info), P(vr_mask_select_info)
     req, hr, hi = P(vr_mask_select_request), P(vr_hist_request), P(vr_hist_info)
     ti, reg = P(vr_mstat_info), P(vr_mstat_region)
+    cam, par, src, pl = P(vr_camera), P(vr_params), P(vr_mview_source), P(vr_mpr_plane)
+    vi, oi = P(vr_mview_info), P(vr_mview_occ_info)
     return {
         "morph": {
             "vr_edt_squared_device": (i32, [vp, ext, vp, u32, u32, vp, u64, ei, vp]),
@@ -466,16 +499,28 @@ def _family_signatures() -> dict:
             "vr_mask_window": (i32, [vp, ext, ext, vp, u32, f32, f32, vp, u64, mi]),
             "vr_mstat_last_kernel_name": name,
         },
+        "mview": {
+            "vr_mview_occupancy_words": (u64, [ext]),
+            "vr_mask_occupancy_device": (i32, [vp, src, vp, u64, oi, vp]),
+            "vr_mask_hit_render_device": (i32, [vp, cam, par, src, ext, vp, u64, vi, vp]),
+            "vr_mask_hit_render": (i32, [vp, cam, par, src, ext, vp, u64, vi]),
+            "vr_mask_pick": (i32, [vp, cam, par, src, u32, u32, P(vr_mask_hit)]),
+            "vr_mask_slice_device": (i32, [vp, pl, src, vp, u64, vi, vp]),
+            "vr_mask_slice": (i32, [vp, pl, src, vp, u64, vi]),
+            "vr_mview_last_kernel_name": name,
+        },
     }
 
 
 # family -> (the environment variable that names its library, the file beside LIB_PATH otherwise)
 FAMILY_LIBS = {"morph": ("VR_AMD_MORPH_LIB", "libvr_amd_morph.so"),
                "maskcc": ("VR_AMD_MASKCC_LIB", "libvr_amd_maskcc.so"),
-               "mstat": ("VR_AMD_MSTAT_LIB", "libvr_amd_mstat.so")}
+               "mstat": ("VR_AMD_MSTAT_LIB", "libvr_amd_mstat.so"),
+               "mview": ("VR_AMD_MVIEW_LIB", "libvr_amd_mview.so")}
 FAMILY_LIB_PATHS = {f: os.environ.get(env) or os.path.join(os.path.dirname(LIB_PATH), so)
                     for f, (env, so) in FAMILY_LIBS.items()}
 MORPH_LIB_PATH, MASKCC_LIB_PATH, MSTAT_LIB_PATH = (FAMILY_LIB_PATHS[f] for f in ("morph", "maskcc", "mstat"))
+MVIEW_LIB_PATH = FAMILY_LIB_PATHS["mview"]
 _FAMILY_LIBS = {}
 
 
@@ -508,6 +553,32 @@ def maskcc_lib() -> C.CDLL:
 
 def mstat_lib() -> C.CDLL:
     return family_lib("mstat")
+
+
+def mview_lib() -> C.CDLL:
+    return family_lib("mview")
+
+
+def mview_source(ext, array_ptr: int, elem_bytes: int, origin=(0, 0, 0), label=None, occupancy_ptr: int = 0,
+                 select=None, reserved: int = 0) -> vr_mview_source:
+    """A vr_mview_source of the (bx, by, bz) = ext grid at `origin`: label None matches every non-zero
+    element (MVIEW_ANY), a label that element alone (MVIEW_LABEL)."""
+    s = vr_mview_source()
+    for a in range(3):
+        s.ext[a] = int(ext[a]) & 0xFFFFFFFF
+        s.origin[a] = int(origin[a]) & 0xFFFFFFFF
+    s.elem_bytes = int(elem_bytes) & 0xFFFFFFFF
+    s.select = (MVIEW_ANY if label is None else MVIEW_LABEL) if select is None else int(select) & 0xFFFFFFFF
+    s.label = 0 if label is None else int(label) & 0xFFFFFFFF
+    s.reserved = int(reserved) & 0xFFFFFFFF
+    s.array = array_ptr or None
+    s.occupancy = occupancy_ptr or None
+    return s
+
+
+def mview_occupancy_words(ext) -> int:
+    """vr_mview_occupancy_words of the (bx, by, bz) grid."""
+    return int(mview_lib().vr_mview_occupancy_words((C.c_uint32 * 3)(*[int(v) & 0xFFFFFFFF for v in ext])))
 
 
 def mstat_region_dict(r: vr_mstat_region) -> dict:
@@ -1395,6 +1466,86 @@ class OffscreenPass:
 
     def mstat_last_kernel_name(self) -> str:
         return mstat_lib().vr_mstat_last_kernel_name(self._ctx).decode()
+
+    # -- the view of a mask or a label array (vr_mview.h, lib/libvr_amd_mview.so) --
+    @staticmethod
+    def _mview_info(info: vr_mview_info) -> dict:
+        return {n: int(getattr(info, n)) for n in ("voxels", "pixels", "covered", "hits", "steps", "samples")}
+
+    @staticmethod
+    def _rect(rect):
+        return None if rect is None else (C.c_uint32 * 4)(*[int(v) & 0xFFFFFFFF for v in rect])
+
+    def _mview_shape(self, rect):
+        w, h = self.size
+        return (h, w) if rect is None else (int(rect[3]), int(rect[2]))
+
+    def mask_occupancy_device(self, source: vr_mview_source, occ_ptr: int, ocap_words: int, stream: int = 0) -> dict:
+        """vr_mask_occupancy_device: the occupancy words of `source` into device memory (ocap_words
+        words) on `stream`; returns the info dict when they are complete."""
+        info = vr_mview_occ_info()
+        self._check(mview_lib().vr_mask_occupancy_device(
+            self._ctx, C.byref(source), C.c_void_p(occ_ptr), int(ocap_words), C.byref(info),
+            C.c_void_p(stream or None)), "mask_occupancy_device")
+        return {n: int(getattr(info, n)) for n in ("voxels", "cells", "cells_set", "matching")}
+
+    def mask_hit_render(self, camera, params, array, origin=(0, 0, 0), label=None, rect=None):
+        """vr_mask_hit_render: ((h, w) records as MVIEW_HIT_DTYPE, info dict) of a (bz, by, bx) uint8 or
+        uint32 host array whose voxel (0, 0, 0) is the volume voxel origin = (x, y, z)."""
+        m, ext, eb = self._morph_mask(array)
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        src = mview_source(ext, m.ctypes.data, eb, origin, label)
+        h, w = self._mview_shape(rect)
+        out = np.zeros(max(h * w, 1), MVIEW_HIT_DTYPE)
+        info = vr_mview_info()
+        self._check(mview_lib().vr_mask_hit_render(
+            self._ctx, C.byref(cam), C.byref(params), C.byref(src), self._rect(rect), out.ctypes.data, h * w,
+            C.byref(info)), "mask_hit_render")
+        return out[:h * w].reshape(h, w), self._mview_info(info)
+
+    def mask_hit_render_device(self, camera, params, source: vr_mview_source, out_ptr: int, rcap: int, rect=None,
+                               stream: int = 0) -> dict:
+        """vr_mask_hit_render_device: the rectangle's records into device memory (rcap records) on
+        `stream`; returns the info dict when they are complete."""
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        info = vr_mview_info()
+        self._check(mview_lib().vr_mask_hit_render_device(
+            self._ctx, C.byref(cam), C.byref(params), C.byref(source), self._rect(rect), C.c_void_p(out_ptr),
+            int(rcap), C.byref(info), C.c_void_p(stream or None)), "mask_hit_render_device")
+        return self._mview_info(info)
+
+    def mask_pick(self, camera, params, source: vr_mview_source, px: int, py: int) -> np.ndarray:
+        """vr_mask_pick: the MVIEW_HIT_DTYPE record of framebuffer pixel (px, py) of a device array."""
+        cam = camera.to_vr_camera() if isinstance(camera, OrbitCamera) else camera
+        out = np.zeros(1, MVIEW_HIT_DTYPE)
+        self._check(mview_lib().vr_mask_pick(
+            self._ctx, C.byref(cam), C.byref(params), C.byref(source), int(px), int(py),
+            C.cast(out.ctypes.data, C.POINTER(vr_mask_hit))), "mask_pick")
+        return out[0]
+
+    def mask_slice(self, plane: vr_mpr_plane, array, origin=(0, 0, 0), label=None):
+        """vr_mask_slice: ((height, width) uint32 elements, info dict) of a host array on `plane`."""
+        m, ext, eb = self._morph_mask(array)
+        src = mview_source(ext, m.ctypes.data, eb, origin, label)
+        n = int(plane.width) * int(plane.height)
+        out = np.zeros(max(n, 1), np.uint32)
+        info = vr_mview_info()
+        self._check(mview_lib().vr_mask_slice(self._ctx, C.byref(plane), C.byref(src), out.ctypes.data, n,
+                                              C.byref(info)), "mask_slice")
+        return out[:n].reshape(int(plane.height), int(plane.width)), self._mview_info(info)
+
+    def mask_slice_device(self, plane: vr_mpr_plane, source: vr_mview_source, out_ptr: int, pcap: int,
+                          stream: int = 0) -> dict:
+        """vr_mask_slice_device: the plane's elements into device memory (pcap uint32) on `stream`;
+        returns the info dict when they are complete."""
+        info = vr_mview_info()
+        self._check(mview_lib().vr_mask_slice_device(
+            self._ctx, C.byref(plane), C.byref(source), C.c_void_p(out_ptr), int(pcap), C.byref(info),
+            C.c_void_p(stream or None)), "mask_slice_device")
+        return self._mview_info(info)
+
+    def mview_last_kernel_name(self) -> str:
+        return mview_lib().vr_mview_last_kernel_name(self._ctx).decode()
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
