@@ -1806,7 +1806,8 @@ void vr_destroy(vr_ctx *c)
                               c->label_dev, c->label_aux_dev, c->label_tab_dev, c->label_out_dev,
                               c->morph_dist_dev, c->morph_tmp_dev, c->morph_cnt_dev, c->morph_io_dev,
                               c->maskcc_lab_dev, c->maskcc_aux_dev, c->maskcc_tab_dev, c->maskcc_io_dev,
-                              c->mstat_aux_dev, c->mstat_io_dev, c->mview_cnt_dev, c->mview_io_dev})
+                              c->mstat_aux_dev, c->mstat_io_dev, c->mview_cnt_dev, c->mview_io_dev,
+                              c->mmesh_aux_dev, c->mmesh_loc_dev, c->mmesh_io_dev, c->mmesh_out_dev})
         if (b.p) hipFree(b.p);
     for (auto e : c->band_ev)
         if (e) hipEventDestroy(e);

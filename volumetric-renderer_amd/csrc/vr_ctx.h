@@ -188,6 +188,13 @@ struct vr_ctx {
     // mview_last_name: the family's last kernel (vr_mview_last_kernel_name)
     DevBlock mview_cnt_dev, mview_io_dev;
     const char *mview_last_name = "";
+    // vr_mask_mesh_count*, vr_mask_mesh_extract* (vr_mmesh.h; csrc/vr_api_mmesh.hip in
+    // lib/libvr_amd_mmesh.so): the inside bits, the words, prefixes and sums of a call
+    // (vr_mmesh_host.h MmeshScratch), the two `local` arrays of the smoothing sweeps, and the host
+    // forms' device copies of their array and of their mesh; all grown on demand.
+    // mmesh_last_name: the family's last kernel (vr_mmesh_last_kernel_name)
+    DevBlock mmesh_aux_dev, mmesh_loc_dev, mmesh_io_dev, mmesh_out_dev;
+    const char *mmesh_last_name = "";
     // vr_debug_label_pass_ms: kernel ms of the last label call's passes (vr_internal.h LabelPassSlot),
     // taken while timing is enabled; 0 for a pass that call did not run
     float label_pass_ms[kLabelPassSlots] = {};

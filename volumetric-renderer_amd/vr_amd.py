@@ -194,6 +194,17 @@ class vr_mview_occ_info(C.Structure):  # vr_mview.h
     _fields_ = [(n, C.c_uint64) for n in ("voxels", "cells", "cells_set", "matching")]
 
 
+class vr_mmesh_request(C.Structure):  # vr_mmesh.h
+    _fields_ = [("ext", C.c_uint32 * 3), ("origin", C.c_uint32 * 3), ("elem_bytes", C.c_uint32),
+                ("select", C.c_uint32), ("label", C.c_uint32), ("closed", C.c_uint32), ("normals", C.c_uint32),
+                ("smooth_iters", C.c_uint32), ("relax", C.c_float), ("reserved", C.c_uint32),
+                ("array", C.c_void_p)]
+
+
+class vr_mmesh_info(C.Structure):  # vr_mmesh.h
+    _fields_ = [(n, C.c_uint64) for n in ("voxels", "vertices", "triangles", "matching")]
+
+
 class vr_dataset(C.Structure):
     _fields_ = [("dims", C.c_uint32 * 3), ("dtype", C.c_int), ("data", C.c_void_p),
                 ("vmin", C.c_float), ("vmax", C.c_float)]
@@ -297,6 +308,13 @@ MVIEW_ANY, MVIEW_LABEL = 0, 1
 MVIEW_MISS = 0xFFFFFFFF
 MVIEW_CELL = 8
 MVIEW_MAX_EXTENT = 32768
+# include/vr/vr_mmesh.h: the surface of a mask, or of one label of a label array, as a triangle mesh
+# with optional cell-constrained smoothing; the entry points live in a sixth library,
+# lib/libvr_amd_mmesh.so (mmesh_lib()), on the same context
+MMESH_SYMBOLS = ["vr_mask_mesh_count_device", "vr_mask_mesh_count", "vr_mask_mesh_extract_device",
+                 "vr_mask_mesh_extract", "vr_mmesh_last_kernel_name"]
+MMESH_MAX_ITERS = 64
+MMESH_MAX_EXTENT = 32768
 # include/vr/vr_debug.h enum vr_exchange (multi-device contexts: how shards reach member 0)
 EXCHANGE_RCCL, EXCHANGE_COPY = 0, 1
 # include/vr/vr_debug.h enum vr_knob (launch-policy overrides: speed only, never results)
@@ -474,6 +492,7 @@ def _family_signatures() -> dict:
     ti, reg = P(vr_mstat_info), P(vr_mstat_region)
     cam, par, src, pl = P(vr_camera), P(vr_params), P(vr_mview_source), P(vr_mpr_plane)
     vi, oi = P(vr_mview_info), P(vr_mview_occ_info)
+    mq, mmi = P(vr_mmesh_request), P(vr_mmesh_info)
     return {
         "morph": {
             "vr_edt_squared_device": (i32, [vp, ext, vp, u32, u32, vp, u64, ei, vp]),
@@ -509,6 +528,13 @@ def _family_signatures() -> dict:
             "vr_mask_slice": (i32, [vp, pl, src, vp, u64, vi]),
             "vr_mview_last_kernel_name": name,
         },
+        "mmesh": {
+            "vr_mask_mesh_count_device": (i32, [vp, mq, mmi, vp]),
+            "vr_mask_mesh_count": (i32, [vp, mq, mmi]),
+            "vr_mask_mesh_extract_device": (i32, [vp, mq, vp, u64, vp, u64, mmi, vp]),
+            "vr_mask_mesh_extract": (i32, [vp, mq, vp, u64, vp, u64, mmi]),
+            "vr_mmesh_last_kernel_name": name,
+        },
     }
 
 
@@ -516,11 +542,13 @@ def _family_signatures() -> dict:
 FAMILY_LIBS = {"morph": ("VR_AMD_MORPH_LIB", "libvr_amd_morph.so"),
                "maskcc": ("VR_AMD_MASKCC_LIB", "libvr_amd_maskcc.so"),
                "mstat": ("VR_AMD_MSTAT_LIB", "libvr_amd_mstat.so"),
-               "mview": ("VR_AMD_MVIEW_LIB", "libvr_amd_mview.so")}
+               "mview": ("VR_AMD_MVIEW_LIB", "libvr_amd_mview.so"),
+               "mmesh": ("VR_AMD_MMESH_LIB", "libvr_amd_mmesh.so")}
 FAMILY_LIB_PATHS = {f: os.environ.get(env) or os.path.join(os.path.dirname(LIB_PATH), so)
                     for f, (env, so) in FAMILY_LIBS.items()}
 MORPH_LIB_PATH, MASKCC_LIB_PATH, MSTAT_LIB_PATH = (FAMILY_LIB_PATHS[f] for f in ("morph", "maskcc", "mstat"))
 MVIEW_LIB_PATH = FAMILY_LIB_PATHS["mview"]
+MMESH_LIB_PATH = FAMILY_LIB_PATHS["mmesh"]
 _FAMILY_LIBS = {}
 
 
@@ -557,6 +585,30 @@ def mstat_lib() -> C.CDLL:
 
 def mview_lib() -> C.CDLL:
     return family_lib("mview")
+
+
+def mmesh_lib() -> C.CDLL:
+    return family_lib("mmesh")
+
+
+def mmesh_request(ext, array_ptr: int, elem_bytes: int, origin=(0, 0, 0), label=None, closed=True, normals=True,
+                  smooth_iters: int = 0, relax: float = 0.5, select=None, reserved: int = 0) -> vr_mmesh_request:
+    """A vr_mmesh_request of the (bx, by, bz) = ext grid at `origin`: label None matches every non-zero
+    element (MVIEW_ANY), a label that element alone (MVIEW_LABEL)."""
+    q = vr_mmesh_request()
+    for a in range(3):
+        q.ext[a] = int(ext[a]) & 0xFFFFFFFF
+        q.origin[a] = int(origin[a]) & 0xFFFFFFFF
+    q.elem_bytes = int(elem_bytes) & 0xFFFFFFFF
+    q.select = (MVIEW_ANY if label is None else MVIEW_LABEL) if select is None else int(select) & 0xFFFFFFFF
+    q.label = 0 if label is None else int(label) & 0xFFFFFFFF
+    q.closed = int(closed) & 0xFFFFFFFF
+    q.normals = int(normals) & 0xFFFFFFFF
+    q.smooth_iters = int(smooth_iters) & 0xFFFFFFFF
+    q.relax = float(relax)
+    q.reserved = int(reserved) & 0xFFFFFFFF
+    q.array = array_ptr or None
+    return q
 
 
 def mview_source(ext, array_ptr: int, elem_bytes: int, origin=(0, 0, 0), label=None, occupancy_ptr: int = 0,
@@ -1546,6 +1598,55 @@ class OffscreenPass:
 
     def mview_last_kernel_name(self) -> str:
         return mview_lib().vr_mview_last_kernel_name(self._ctx).decode()
+
+    # -- the surface of a mask or of one label as a mesh (vr_mmesh.h, lib/libvr_amd_mmesh.so) --
+    @staticmethod
+    def _mmesh_info(info: vr_mmesh_info) -> dict:
+        return {n: int(getattr(info, n)) for n in ("voxels", "vertices", "triangles", "matching")}
+
+    def mask_mesh_count(self, array, origin=(0, 0, 0), label=None, closed=True) -> dict:
+        """vr_mask_mesh_count: the info dict of a (bz, by, bx) uint8 or uint32 host array whose voxel
+        (0, 0, 0) is the volume voxel origin = (x, y, z)."""
+        m, ext, eb = self._morph_mask(array)
+        req = mmesh_request(ext, m.ctypes.data, eb, origin, label, closed)
+        info = vr_mmesh_info()
+        self._check(mmesh_lib().vr_mask_mesh_count(self._ctx, C.byref(req), C.byref(info)), "mask_mesh_count")
+        return self._mmesh_info(info)
+
+    def mask_mesh_count_device(self, request: vr_mmesh_request, stream: int = 0) -> dict:
+        """vr_mask_mesh_count_device: the info dict of a device array, known when it returns."""
+        info = vr_mmesh_info()
+        self._check(mmesh_lib().vr_mask_mesh_count_device(self._ctx, C.byref(request), C.byref(info),
+                                                          C.c_void_p(stream or None)), "mask_mesh_count_device")
+        return self._mmesh_info(info)
+
+    def mask_mesh_extract(self, array, origin=(0, 0, 0), label=None, closed=True, normals=True, smooth_iters: int = 0,
+                          relax: float = 0.5):
+        """vr_mask_mesh_extract: (vertices as MESH_VERTEX_DTYPE records, triangles (T, 3) uint32, info
+        dict) of a host array.  Sized by vr_mask_mesh_count first."""
+        m, ext, eb = self._morph_mask(array)
+        req = mmesh_request(ext, m.ctypes.data, eb, origin, label, closed, normals, smooth_iters, relax)
+        info = vr_mmesh_info()
+        self._check(mmesh_lib().vr_mask_mesh_count(self._ctx, C.byref(req), C.byref(info)), "mask_mesh_count")
+        nv, nt = int(info.vertices), int(info.triangles)
+        verts = np.zeros(max(nv, 1), MESH_VERTEX_DTYPE)  # (never a NULL buffer)
+        tris = np.zeros((max(nt, 1), 3), np.uint32)
+        self._check(mmesh_lib().vr_mask_mesh_extract(self._ctx, C.byref(req), verts.ctypes.data, nv, tris.ctypes.data,
+                                                     nt, C.byref(info)), "mask_mesh_extract")
+        return verts[:nv], tris[:nt], self._mmesh_info(info)
+
+    def mask_mesh_extract_device(self, request: vr_mmesh_request, verts_ptr: int, vcap: int, tris_ptr: int, tcap: int,
+                                 stream: int = 0) -> dict:
+        """vr_mask_mesh_extract_device: the mesh of a device array into device memory (vcap vertex
+        records, tcap triangles) on `stream`; returns the info dict when both buffers are complete."""
+        info = vr_mmesh_info()
+        self._check(mmesh_lib().vr_mask_mesh_extract_device(
+            self._ctx, C.byref(request), C.c_void_p(verts_ptr), int(vcap), C.c_void_p(tris_ptr), int(tcap),
+            C.byref(info), C.c_void_p(stream or None)), "mask_mesh_extract_device")
+        return self._mmesh_info(info)
+
+    def mmesh_last_kernel_name(self) -> str:
+        return mmesh_lib().vr_mmesh_last_kernel_name(self._ctx).decode()
 
     def count_work_mpr(self, plane: vr_mpr_plane, params: Optional[vr_params] = None) -> dict:
         p = params if params is not None else default_params()
