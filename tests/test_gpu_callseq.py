@@ -32,11 +32,11 @@ import hist_ref
 import mesh_scenes
 import synth
 import vr_amd
+from gpu_kit import GUARD32, c_plane
 from hit_scenes import words
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x77777777
 SLACK = 64
 P = vr_amd.default_params
 
@@ -54,13 +54,13 @@ def streams(gpu):
     return [torch.cuda.Stream() for _ in range(4)]
 
 
-def guarded(nwords):
-    return np.full(int(nwords) + SLACK, GUARD, np.uint32)
+def host_guarded(nwords):
+    return np.full(int(nwords) + SLACK, GUARD32, np.uint32)
 
 
 def dev_guarded(nwords):
     import torch
-    return torch.full((int(nwords) + SLACK,), GUARD, dtype=torch.int32, device="cuda")
+    return torch.full((int(nwords) + SLACK,), GUARD32, dtype=torch.int32, device="cuda")
 
 
 def host(t):
@@ -101,7 +101,7 @@ class Replay:
         self.ok(bad == 0, f"{what}: {bad} of {g.size} words differ from the reference")
 
     def guard(self, what, tail):
-        bad = int((np.asarray(tail) != GUARD).sum())
+        bad = int((np.asarray(tail) != GUARD32).sum())
         self.ok(bad == 0, f"{what}: {bad} guard words past the output were written")
 
     def rc(self, rc, what):
@@ -167,7 +167,7 @@ class Replay:
         req = vr_amd.vr_hist_request()
         req.lo, req.hi, req.nbins = spec["lo"], spec["hi"], spec["nbins"]
         box_req(req, spec["box"])
-        bins = guarded(2 * spec["nbins"])
+        bins = host_guarded(2 * spec["nbins"])
         info = vr_amd.vr_hist_info()
         self.rc(self.L.vr_histogram(self.rp._ctx, C.byref(req), bins.ctypes.data_as(C.POINTER(C.c_uint64)),
                                     C.byref(info)), "vr_histogram")
@@ -195,7 +195,7 @@ class Replay:
         got = rp.mesh_count(*args)
         self.ok(got == ref.info, f"mesh_count {got}, the reference {ref.info}")
         nv, nt = ref.info["vertices"], ref.info["triangles"]
-        hv, ht = guarded(nv * 6), guarded(nt * 3)
+        hv, ht = host_guarded(nv * 6), host_guarded(nt * 3)
         info = vr_amd.vr_mesh_info()
         req = vr_amd.mesh_request(*args)
         self.rc(self.L.vr_mesh_extract(rp._ctx, C.byref(req), hv.ctypes.data, nv, ht.ctypes.data, nt, C.byref(info)),
@@ -229,7 +229,7 @@ class Replay:
         got = rp.label_count(*args)
         self.ok(got == want, f"label_count {got}, the reference {want}")
         n, nc = want["voxels"], want["components"]
-        hl, hc = guarded(n), guarded(nc * 16)
+        hl, hc = host_guarded(n), host_guarded(nc * 16)
         info = vr_amd.vr_label_info()
         req = vr_amd.label_request(*args)
         self.rc(self.L.vr_label_components(rp._ctx, C.byref(req), hl.ctypes.data, n, hc.ctypes.data, nc,
@@ -238,7 +238,7 @@ class Replay:
         for grown in (inside, outside):
             if grown is None:
                 continue
-            hm = guarded((n + 3) // 4)
+            hm = host_guarded((n + 3) // 4)
             comp = vr_amd.vr_label_component()
             sd = (C.c_uint32 * 3)(*grown[0])
             self.rc(self.L.vr_region_grow(rp._ctx, C.byref(req), sd, hm.ctypes.data, n, C.byref(comp)),
@@ -255,7 +255,7 @@ class Replay:
         rp = self.rp
         cam, p = Q.camera(op["cam"]), P()
         kind, th, rect = Q.HIT_KINDS[op["hit"]], op["threshold"], op["rect"]
-        out = guarded(rect[2] * rect[3] * 6)
+        out = host_guarded(rect[2] * rect[3] * 6)
         req = vr_amd.hit_request(kind, th, rect)
         self.rc(self.L.vr_hit_render(rp._ctx, C.byref(cam), C.byref(p), C.byref(req), out.ctypes.data), "vr_hit_render")
         # (words() makes every NaN value one NaN, as the per-feature test compares them)
@@ -369,11 +369,6 @@ class Replay:
                 keys = ("evictions", "downgrades", "last_downgrade")
                 self.ok(all(before[k] == after[k] for k in keys),
                         f"{op['op']} changed the memory report: {before} -> {after}")
-
-
-def c_plane(pl):
-    return vr_amd.mpr_plane(pl["origin"], pl["du"], pl["dv"], pl["dn"], pl["width"], pl["height"],
-                            pl["nsamples"], pl["op"])
 
 
 @pytest.mark.parametrize("seed", Q.SEEDS)

@@ -23,6 +23,8 @@ import pyoracle
 import range_scenes
 import synth
 import vr_amd
+from gpu_kit import GUARD32
+from gpu_kit import stream  # noqa: F401
 from test_gpu_hit import check_records
 from test_gpu_iso import check_against as check_iso
 from test_gpu_label import NAME as LABEL_NAME
@@ -36,7 +38,6 @@ pytestmark = pytest.mark.gpu
 
 F = np.float32
 INF = float("inf")
-GUARD = 0x77777777
 SLACK = 64
 P = vr_amd.default_params
 
@@ -47,17 +48,11 @@ def dims_id(d):
 
 def dev_guarded(nwords):
     import torch
-    return torch.full((int(nwords) + SLACK,), GUARD, dtype=torch.int32, device="cuda")
+    return torch.full((int(nwords) + SLACK,), GUARD32, dtype=torch.int32, device="cuda")
 
 
 def host(t):
     return t.cpu().numpy().view(np.uint32)
-
-
-@pytest.fixture(scope="module")
-def stream(gpu):
-    import torch
-    return torch.cuda.Stream()
 
 
 def label_into_guarded(rp, ref, lo, hi, conn, box, stream, what):
@@ -72,7 +67,7 @@ def label_into_guarded(rp, ref, lo, hi, conn, box, stream, what):
     hl, hc = host(dl), host(dc)
     assert info == want, (what, info, want)
     assert hl[:n].tobytes() == labels.tobytes() and hc[:nc * 16].tobytes() == rec.tobytes(), what
-    assert np.all(hl[n:] == GUARD) and np.all(hc[nc * 16:] == GUARD), (what, "written past the counts")
+    assert np.all(hl[n:] == GUARD32) and np.all(hc[nc * 16:] == GUARD32), (what, "written past the counts")
     return hl[:n], hc[:nc * 16]
 
 
@@ -115,7 +110,7 @@ def mesh_into_guarded(rp, ref, iso, closed, normals, box, stream, what, canonica
     assert nt == 0 or int(tris.max()) < nv, what
     if canonical:
         mesh_scenes.assert_same_mesh((verts, tris), (ref.verts, ref.tris), what)
-    assert np.all(hv[nv * 6:] == GUARD) and np.all(ht[nt * 3:] == GUARD), (what, "written past the counts")
+    assert np.all(hv[nv * 6:] == GUARD32) and np.all(ht[nt * 3:] == GUARD32), (what, "written past the counts")
     return hv[:nv * 6], ht[:nt * 3]
 
 

@@ -16,6 +16,7 @@ import label_ref
 import label_scenes as S
 import synth
 import vr_amd
+from gpu_kit import GUARD32
 from range_scenes import STORAGE, volume
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,6 @@ INF = float("inf")
 NAME = "void vr::(anonymous namespace)::label_local_kernel<%s, %d>(vr::LabelArgs)"
 TAG = {(0, 0): "unsigned char", (1, 0): "signed char", (0, 1): "vr::Quad8<unsigned char>",
        (1, 1): "vr::Quad8<signed char>", (2, None): "unsigned short", (3, None): "short", (4, None): "float"}
-GUARD = 0x77777777
 
 
 def label_pass(vol, w=16, h=16, vrange=None, **knobs):
@@ -226,8 +226,8 @@ def test_two_calls_write_identical_bytes_and_the_device_form_equals_the_host_for
         n, nc = i1["voxels"], i1["components"]
         assert nc >= 40
         stream = torch.cuda.Stream()
-        dl = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-        dc = torch.full((nc * 16 + 16,), GUARD, dtype=torch.int32, device="cuda")
+        dl = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+        dc = torch.full((nc * 16 + 16,), GUARD32, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         info = rp.label_device(dl.data_ptr(), n + 3, dc.data_ptr(), nc + 1, lo, hi, conn, box,
                                stream=stream.cuda_stream)
@@ -235,7 +235,7 @@ def test_two_calls_write_identical_bytes_and_the_device_form_equals_the_host_for
         hl, hc = dl.cpu().numpy().view(np.uint32), dc.cpu().numpy().view(np.uint32)
         assert info == i1
         assert hl[:n].tobytes() == l1.tobytes() and hc[:nc * 16].tobytes() == r1.tobytes()
-        assert np.all(hl[n:] == GUARD) and np.all(hc[nc * 16:] == GUARD)
+        assert np.all(hl[n:] == GUARD32) and np.all(hc[nc * 16:] == GUARD32)
 
 
 # ---- 7. errors ------------------------------------------------------------------------------------------------
@@ -246,11 +246,11 @@ def test_every_error_leaves_the_outputs_untouched(gpu, scene_pass):
     lo, hi = 0.7, 1.0
     want_labels, want_rec, want = S.reference("noise", lo, hi, 6, None)
     n, nc = want["voxels"], want["components"]
-    hl = np.full(n, GUARD, np.uint32)
-    hc = np.full(nc * 16, GUARD, np.uint32)
+    hl = np.full(n, GUARD32, np.uint32)
+    hc = np.full(nc * 16, GUARD32, np.uint32)
     hm = np.full(n, 0x77, np.uint8)
-    dl = torch.full((n,), GUARD, dtype=torch.int32, device="cuda")
-    dc = torch.full((nc * 16,), GUARD, dtype=torch.int32, device="cuda")
+    dl = torch.full((n,), GUARD32, dtype=torch.int32, device="cuda")
+    dc = torch.full((nc * 16,), GUARD32, dtype=torch.int32, device="cuda")
     dm = torch.full((n,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     info = vr_amd.vr_label_info()
@@ -259,8 +259,8 @@ def test_every_error_leaves_the_outputs_untouched(gpu, scene_pass):
 
     def untouched():
         torch.cuda.synchronize()
-        return (np.all(hl == GUARD) and np.all(hc == GUARD) and np.all(hm == 0x77) and bool((dl == GUARD).all())
-                and bool((dc == GUARD).all()) and bool((dm == 0x77).all()))
+        return (np.all(hl == GUARD32) and np.all(hc == GUARD32) and np.all(hm == 0x77) and bool((dl == GUARD32).all())
+                and bool((dc == GUARD32).all()) and bool((dm == 0x77).all()))
 
     def label_calls(req, lcap=n, ccap=nc, inf=info, bufs=True):
         rq = C.byref(req) if req is not None else None
@@ -348,9 +348,9 @@ def test_every_error_leaves_the_outputs_untouched(gpu, scene_pass):
         assert vr_amd.OffscreenPass._label_info(info) == want and info.reserved == 0
         torch.cuda.synchronize()
         assert hl.tobytes() == want_labels.tobytes() == dl.cpu().numpy().tobytes()
-        assert np.all(hc == GUARD) and bool((dc == GUARD).all())
-        hl[:] = GUARD
-        dl.fill_(GUARD)
+        assert np.all(hc == GUARD32) and bool((dc == GUARD32).all())
+        hl[:] = GUARD32
+        dl.fill_(GUARD32)
         hm[:] = 0x77
         dm.fill_(0x77)
     # and the context still works

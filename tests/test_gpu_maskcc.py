@@ -17,10 +17,10 @@ import maskcc_scenes as S
 import morph_ref
 import synth
 import vr_amd
+from gpu_kit import GUARD32, context_untouched, device_bytes, ext_of
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x77777777
 INF = float("inf")
 DT = vr_amd.LABEL_COMPONENT_DTYPE
 
@@ -32,27 +32,12 @@ def rp(gpu):
     p.close()
 
 
-def ext_of(m):
-    return (m.shape[2], m.shape[1], m.shape[0])
-
-
-def device_mask(m, odd=False):
-    """The mask in device memory (a torch tensor to keep, the pointer); odd: at an odd address."""
-    import torch
-    b = np.frombuffer(np.ascontiguousarray(m).tobytes(), np.uint8)
-    t = torch.full((b.size + 8,), 0x55, dtype=torch.uint8, device="cuda")
-    off = 1 if odd else 0
-    t[off:off + b.size] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + off
-
-
 def label_device(rp, m, conn, ncomps, odd=False, ccap=None):
     """vr_mask_label_device on a stream of its own -> (labels, records, info); the records at an odd
     address, guard words past every buffer, the mask unchanged."""
     import torch
-    keep, ptr = device_mask(m, odd)
-    dl = torch.full((m.size + 8,), GUARD, dtype=torch.int32, device="cuda")
+    keep, ptr = device_bytes(m, odd)
+    dl = torch.full((m.size + 8,), GUARD32, dtype=torch.int32, device="cuda")
     dc = torch.full((ncomps * 64 + 17,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
@@ -61,14 +46,14 @@ def label_device(rp, m, conn, ncomps, odd=False, ccap=None):
     # (complete on return: no synchronisation of ours before the copies on another stream)
     hl = dl.cpu().numpy().view(np.uint32)
     hc = dc.cpu().numpy()
-    assert np.all(hl[m.size:] == GUARD) and hc[0] == 0x77 and np.all(hc[1 + ncomps * 64:] == 0x77)
+    assert np.all(hl[m.size:] == GUARD32) and hc[0] == 0x77 and np.all(hc[1 + ncomps * 64:] == 0x77)
     assert keep.cpu().numpy()[(1 if odd else 0):][:m.nbytes].tobytes() == m.tobytes()  # the mask is only read
     return hl[:m.size].reshape(m.shape), np.frombuffer(hc[1:1 + ncomps * 64].tobytes(), DT), info
 
 
 def select_device(rp, m, rule, conn=6, min_voxels=0, seed=(0, 0, 0), odd=False):
     import torch
-    keep, ptr = device_mask(m, odd)
+    keep, ptr = device_bytes(m, odd)
     o = torch.full((m.size + 9,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
@@ -124,10 +109,10 @@ def test_the_window_labelling_is_the_oracle_at_volume_size(gpu, name, lo, hi):
             key = (name, lo, hi, conn, None)
             pinned = label_scenes.CASES.get(key, label_scenes.LONG_CASES.get(key))  # (where the scenes pin one)
             nc = rp.label_count(lo, hi, conn)["components"]
-            dl = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-            dc = torch.full((nc * 16 + 16,), GUARD, dtype=torch.int32, device="cuda")
-            ml = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-            mc = torch.full((nc * 16 + 16,), GUARD, dtype=torch.int32, device="cuda")
+            dl = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+            dc = torch.full((nc * 16 + 16,), GUARD32, dtype=torch.int32, device="cuda")
+            ml = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+            mc = torch.full((nc * 16 + 16,), GUARD32, dtype=torch.int32, device="cuda")
             torch.cuda.synchronize()
             winfo = rp.label_device(dl.data_ptr(), n, dc.data_ptr(), nc, lo, hi, conn, None, stream=stream.cuda_stream)
             assert winfo["components"] == nc > 0 and (pinned is None or label_scenes.pinned(winfo) == pinned)
@@ -210,9 +195,9 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     want, wrec, winfo = S.reference_label(name, 6)
     nc = winfo["components"]
     ext = (C.c_uint32 * 3)(*ext_of(m))
-    keep, mp = device_mask(S.as_labels(m))
-    dl = torch.full((n + 4,), GUARD, dtype=torch.int32, device="cuda")
-    dc = torch.full((nc * 16 + 4,), GUARD, dtype=torch.int32, device="cuda")
+    keep, mp = device_bytes(S.as_labels(m))
+    dl = torch.full((n + 4,), GUARD32, dtype=torch.int32, device="cuda")
+    dc = torch.full((nc * 16 + 4,), GUARD32, dtype=torch.int32, device="cuda")
     o = torch.full((n + 4,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     li, si = vr_amd.vr_label_info(), vr_amd.vr_mask_select_info()
@@ -236,7 +221,7 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     assert label(lcap=n - 1) == -28 and b"smaller" in vr_amd.lib().vr_last_error(rp._ctx)
     assert (li.voxels, li.in_voxels, li.components, li.largest_voxels, li.largest_label) == (n, 0, 0, 0, 0)
     assert select(cap=n - 1) == -28 and (si.voxels, si.in_set, si.out_set, si.components, si.kept) == (n, 0, 0, 0, 0)
-    hl = np.full(n, GUARD, np.uint32)
+    hl = np.full(n, GUARD32, np.uint32)
     hc = np.full(nc * 64, 0x77, np.uint8)
     ho = np.full(n, 0x77, np.uint8)
     req = vr_amd.mask_select_request(0)
@@ -259,8 +244,8 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     assert bad == [-22] * len(bad), bad
     assert bytes(li) == b"\x77" * 40 and bytes(si) == b"\x77" * 40
     torch.cuda.synchronize()
-    assert np.all(dl.cpu().numpy().view(np.uint32) == GUARD) and np.all(dc.cpu().numpy().view(np.uint32) == GUARD)
-    assert np.all(o.cpu().numpy() == 0x77) and np.all(hl == GUARD) and np.all(hc == 0x77) and np.all(ho == 0x77)
+    assert np.all(dl.cpu().numpy().view(np.uint32) == GUARD32) and np.all(dc.cpu().numpy().view(np.uint32) == GUARD32)
+    assert np.all(o.cpu().numpy() == 0x77) and np.all(hl == GUARD32) and np.all(hc == 0x77) and np.all(ho == 0x77)
     assert keep.cpu().numpy()[:4 * n].tobytes() == S.as_labels(m).tobytes()
     # a seed outside the grid is KEEP_SEED's error alone
     assert select(rule=0, seed=(bx, by, bz)) == 0 and select(rule=3, seed=(bx, by, bz)) == 0
@@ -269,7 +254,7 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     assert nc > 1 and label(ccap=nc - 1) == -28 and b"record" in vr_amd.lib().vr_last_error(rp._ctx)
     assert vr_amd.OffscreenPass._label_info(li) == winfo
     assert dl.cpu().numpy().view(np.uint32)[:n].tobytes() == want.tobytes()
-    assert np.all(dc.cpu().numpy().view(np.uint32) == GUARD)
+    assert np.all(dc.cpu().numpy().view(np.uint32) == GUARD32)
     fresh()
     assert L.vr_mask_label(rp._ctx, ext, m.ctypes.data, 1, 6, hl.ctypes.data, n, hc.ctypes.data, nc - 1, C.byref(li)) == -28
     assert vr_amd.OffscreenPass._label_info(li) == winfo and hl.tobytes() == want.tobytes() and np.all(hc == 0x77)
@@ -310,59 +295,54 @@ def test_the_chain_from_a_click_to_a_distance_stays_on_the_device(gpu, name, lo,
 
     rp = hit_scenes.hit_pass(32, 24, np.asarray(vol), synth.tf_color(), 0.5)
     try:
-        cam = synth.camera("rotA").to_vr_camera()
-        p = vr_amd.default_params(shading=1, skip_empty=1)
-        before = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        rep = rp.memory_report()
-        assert rp.maskcc_last_kernel_name() == ""  # a fresh context
-        a = torch.full((n + 16,), 0x77, dtype=torch.uint8, device="cuda")
-        b = torch.full((n + 16,), 0x77, dtype=torch.uint8, device="cuda")
-        dd = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        stream = torch.cuda.Stream()
-        s = stream.cuda_stream
-        rp.timing_enable(True)
-        assert rp.region_grow_device(seed, a.data_ptr(), n, lo, hi, 6, None, stream=s) == comp
-        last = rp.last_kernel_name()  # (the label family's: the calls after it leave the name alone)
-        assert rp.morph_device(ext, vr_amd.MORPH_OPEN, r2, a.data_ptr(), 1, b.data_ptr(), n, stream=s) == open_info
-        rp.timing_reset()
-        assert rp.mask_select_device(ext, vr_amd.MASK_KEEP_SEED, b.data_ptr(), 1, a.data_ptr(), n, 6, seed=seed,
-                                     stream=s) == kept_info
-        assert rp.timing_read()[1] == 3  # the labelling passes, the records, the selection
-        ms = rp.maskcc_pass_ms()  # (the bench's split of those intervals, kernel by kernel)
-        assert list(ms) == list(rp.MASKCC_PASSES) and all(v > 0.0 for v in ms.values()), ms
-        assert rp.maskcc_last_kernel_name() == "mcc_select_kernel<0>"
-        rp.timing_reset()
-        assert rp.mask_select_device(ext, vr_amd.MASK_FILL_HOLES, a.data_ptr(), 1, b.data_ptr(), n, 6,
-                                     stream=s) == fill_info
-        assert rp.timing_read()[1] == 3
-        assert rp.maskcc_last_kernel_name() == "mcc_select_kernel<1>"
-        assert rp.distance_transform_device(ext, b.data_ptr(), 1, dd.data_ptr(), n, to_set=False, stream=s) == dist_info
-        ha, hb, hd = a.cpu().numpy(), b.cpu().numpy(), dd.cpu().numpy().view(np.uint32)
-        assert ha[:n].tobytes() == kept.tobytes() and hb[:n].tobytes() == filled.tobytes()
-        assert hd[:n].tobytes() == dist.tobytes()
-        assert np.all(ha[n:] == 0x77) and np.all(hb[n:] == 0x77) and np.all(hd[n:] == GUARD)
-        # the labels of the filled piece: two intervals, and one where there is no component
-        dl = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-        dc = torch.full((16 + 16,), GUARD, dtype=torch.int32, device="cuda")
-        torch.cuda.synchronize()
-        rp.timing_reset()
-        flab, frec, finfo = R.label(filled, 6)
-        assert rp.mask_label_device(ext, b.data_ptr(), 1, dl.data_ptr(), n, dc.data_ptr(), 1, 6, stream=s) == finfo
-        assert rp.timing_read()[1] == 2 and finfo["components"] == 1
-        assert dl.cpu().numpy().view(np.uint32)[:n].tobytes() == flab.tobytes()
-        assert rp.maskcc_last_kernel_name() == "mcc_largest_kernel"
-        rp.timing_reset()
-        assert rp.mask_label(np.zeros((3, 4, 5), np.uint8))[2]["components"] == 0
-        assert rp.timing_read()[1] == 1 and rp.maskcc_last_kernel_name() == "mcc_scan_kernel"
-        ms = rp.maskcc_pass_ms()
-        assert all((v > 0.0) == (k in ("rows", "link", "flatten", "scan")) for k, v in ms.items()), ms
-        rp.timing_enable(False)
-        rp.timing_reset()
-        rp.mask_select(S.mask("hole_block"), vr_amd.MASK_FILL_HOLES, 6)
-        assert rp.timing_read()[1] == 0 and not any(rp.maskcc_pass_ms().values())
-        assert rp.memory_report() == rep and rp.last_kernel_name() == last
-        assert np.array_equal(rp.render(cam, p, vr_amd.OUT_RGBA32F).view(np.uint32), before.view(np.uint32))
+        with context_untouched(rp) as state:
+            assert rp.maskcc_last_kernel_name() == ""  # a fresh context
+            a = torch.full((n + 16,), 0x77, dtype=torch.uint8, device="cuda")
+            b = torch.full((n + 16,), 0x77, dtype=torch.uint8, device="cuda")
+            dd = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            stream = torch.cuda.Stream()
+            s = stream.cuda_stream
+            rp.timing_enable(True)
+            assert rp.region_grow_device(seed, a.data_ptr(), n, lo, hi, 6, None, stream=s) == comp
+            state.rebase()  # (the label family's name: the calls after it leave the name alone)
+            assert rp.morph_device(ext, vr_amd.MORPH_OPEN, r2, a.data_ptr(), 1, b.data_ptr(), n, stream=s) == open_info
+            rp.timing_reset()
+            assert rp.mask_select_device(ext, vr_amd.MASK_KEEP_SEED, b.data_ptr(), 1, a.data_ptr(), n, 6, seed=seed,
+                                         stream=s) == kept_info
+            assert rp.timing_read()[1] == 3  # the labelling passes, the records, the selection
+            ms = rp.maskcc_pass_ms()  # (the bench's split of those intervals, kernel by kernel)
+            assert list(ms) == list(rp.MASKCC_PASSES) and all(v > 0.0 for v in ms.values()), ms
+            assert rp.maskcc_last_kernel_name() == "mcc_select_kernel<0>"
+            rp.timing_reset()
+            assert rp.mask_select_device(ext, vr_amd.MASK_FILL_HOLES, a.data_ptr(), 1, b.data_ptr(), n, 6,
+                                         stream=s) == fill_info
+            assert rp.timing_read()[1] == 3
+            assert rp.maskcc_last_kernel_name() == "mcc_select_kernel<1>"
+            assert rp.distance_transform_device(ext, b.data_ptr(), 1, dd.data_ptr(), n, to_set=False, stream=s) == dist_info
+            ha, hb, hd = a.cpu().numpy(), b.cpu().numpy(), dd.cpu().numpy().view(np.uint32)
+            assert ha[:n].tobytes() == kept.tobytes() and hb[:n].tobytes() == filled.tobytes()
+            assert hd[:n].tobytes() == dist.tobytes()
+            assert np.all(ha[n:] == 0x77) and np.all(hb[n:] == 0x77) and np.all(hd[n:] == GUARD32)
+            # the labels of the filled piece: two intervals, and one where there is no component
+            dl = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+            dc = torch.full((16 + 16,), GUARD32, dtype=torch.int32, device="cuda")
+            torch.cuda.synchronize()
+            rp.timing_reset()
+            flab, frec, finfo = R.label(filled, 6)
+            assert rp.mask_label_device(ext, b.data_ptr(), 1, dl.data_ptr(), n, dc.data_ptr(), 1, 6, stream=s) == finfo
+            assert rp.timing_read()[1] == 2 and finfo["components"] == 1
+            assert dl.cpu().numpy().view(np.uint32)[:n].tobytes() == flab.tobytes()
+            assert rp.maskcc_last_kernel_name() == "mcc_largest_kernel"
+            rp.timing_reset()
+            assert rp.mask_label(np.zeros((3, 4, 5), np.uint8))[2]["components"] == 0
+            assert rp.timing_read()[1] == 1 and rp.maskcc_last_kernel_name() == "mcc_scan_kernel"
+            ms = rp.maskcc_pass_ms()
+            assert all((v > 0.0) == (k in ("rows", "link", "flatten", "scan")) for k, v in ms.items()), ms
+            rp.timing_enable(False)
+            rp.timing_reset()
+            rp.mask_select(S.mask("hole_block"), vr_amd.MASK_FILL_HOLES, 6)
+            assert rp.timing_read()[1] == 0 and not any(rp.maskcc_pass_ms().values())
     finally:
         rp.close()
 

@@ -40,16 +40,12 @@ import maskseq as M
 import mstat_ref
 import synth
 import vr_amd
+from gpu_kit import c_plane
 
 pytestmark = pytest.mark.gpu
 
 FAMILIES = ("morph", "maskcc", "mstat", "mview")
 REPORT_KEYS = ("builds", "evictions", "downgrades", "last_downgrade")
-
-
-def c_plane(pl):
-    return vr_amd.mpr_plane(pl["origin"], pl["du"], pl["dv"], pl["dn"], pl["width"], pl["height"], pl["nsamples"],
-                            pl["op"])
 
 
 class Pass(vr_amd.OffscreenPass):

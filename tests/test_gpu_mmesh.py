@@ -17,22 +17,13 @@ import mmesh_scenes as S
 import morph_ref
 import synth
 import vr_amd
+from gpu_kit import GUARD, context_untouched, device_bytes, err, first_difference, guarded, read_guarded, unchanged
+from gpu_kit import stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-GUARD = 0x77
 VB, TB = 24, 12  # bytes of a vertex record and of a triangle
-
-
-@pytest.fixture(scope="module")
-def stream(gpu):
-    import torch
-    return torch.cuda.Stream()
-
-
-def err(rp):
-    return vr_amd.lib().vr_last_error(rp._ctx).decode()
 
 
 def ramp(dims):
@@ -63,39 +54,6 @@ def passes(gpu):
         rp.close()
 
 
-def device_bytes(a, odd=False):
-    """The array's bytes in device memory (a tensor to keep, the pointer), 0x55 around them; odd: at
-    an odd address (byte masks)."""
-    import torch
-    b = np.frombuffer(np.ascontiguousarray(a).tobytes(), np.uint8)
-    t = torch.full((b.size + 16,), 0x55, dtype=torch.uint8, device="cuda")
-    off = 1 if odd else 0
-    t[off:off + b.size] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + off
-
-
-def unchanged(keep, a, odd=False):
-    h = keep.cpu().numpy()
-    off = 1 if odd else 0
-    return h[off:off + a.nbytes].tobytes() == a.tobytes() and np.all(h[:off] == 0x55) and np.all(h[off + a.nbytes:] == 0x55)
-
-
-def guarded(nbytes):
-    """A device buffer of nbytes at a 4-byte (not 8-byte) aligned address with guard bytes around it."""
-    import torch
-    t = torch.full((nbytes + 24,), GUARD, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    off = 4 if t.data_ptr() % 8 == 0 else 8 - t.data_ptr() % 8 + 4
-    return t, t.data_ptr() + off, off
-
-
-def read_guarded(t, off, nbytes):
-    h = t.cpu().numpy()
-    assert np.all(h[:off] == GUARD) and np.all(h[off + nbytes:] == GUARD)
-    return h[off:off + nbytes].tobytes()
-
-
 class Source:
     """A scene's array in device memory (a byte mask at an odd address) and its requests."""
 
@@ -120,15 +78,6 @@ class Source:
 
     def intact(self):
         return unchanged(self.keep, self.array, self.odd)
-
-
-def first_difference(got, want, rec):
-    g = np.frombuffer(got, np.uint32).reshape(-1, rec // 4)
-    w = np.frombuffer(want, np.uint32).reshape(-1, rec // 4)
-    if g.shape != w.shape:
-        return g.shape, w.shape
-    bad = np.nonzero((g != w).any(1))[0]
-    return (int(bad.size), int(bad[0]), g[bad[0]].tolist(), w[bad[0]].tolist()) if bad.size else None
 
 
 def check(src, what, **kw):
@@ -363,35 +312,29 @@ def test_the_calls_leave_the_context_as_it_was(gpu, stream):
     a, dims, origin, label = S.scene("ball")
     rp = make_pass(mesh_scenes.small_ball())
     try:
-        cam = synth.camera("rotA").to_vr_camera()
-        p = vr_amd.default_params(shading=1, skip_empty=1)
-        before = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        rep = rp.memory_report()
-        last = rp.last_kernel_name()
-        assert rp.mmesh_last_kernel_name() == ""  # a fresh context
-        src = Source(rp, stream, "ball")
-        rp.timing_enable(True)
-        rp.timing_reset()
-        assert rp.mask_mesh_count_device(src.request(), stream=src.st) == S.reference("ball").info
-        assert rp.timing_read()[1] == 1 and rp.mmesh_last_kernel_name() == "mmesh_scan_kernel"
-        rp.timing_reset()
-        check(src, "ball", closed=True, normals=True, smooth_iters=5, relax=0.5)
-        assert rp.timing_read()[1] == 1 and rp.mmesh_last_kernel_name() == "mmesh_triangle_kernel"
-        rp.timing_reset()
-        info = vr_amd.vr_mmesh_info()
-        req = src.request()
-        vt, vptr, voff = guarded(VB)
-        tt, tptr, toff = guarded(TB)
-        assert vr_amd.mmesh_lib().vr_mask_mesh_extract_device(rp._ctx, C.byref(req), vptr, 1, tptr, 1, C.byref(info),
-                                                              src.st) == -28
-        assert rp.timing_read()[1] == 1  # the count pass ran, and its interval is whole
-        rp.timing_enable(False)
-        rp.timing_reset()
-        v, t, hinfo = rp.mask_mesh_extract(a, origin, label, True, True, 5, 0.5)
-        want = S.reference("ball", closed=True, normals=True, smooth_iters=5, relax=0.5)
-        assert rp.timing_read()[1] == 0 and v.tobytes() == want.verts.tobytes() and t.tobytes() == want.tris.tobytes()
-        assert rp.memory_report() == rep and rp.last_kernel_name() == last
-        assert np.array_equal(rp.render(cam, p, vr_amd.OUT_RGBA32F).view(np.uint32), before.view(np.uint32))
+        with context_untouched(rp):
+            assert rp.mmesh_last_kernel_name() == ""  # a fresh context
+            src = Source(rp, stream, "ball")
+            rp.timing_enable(True)
+            rp.timing_reset()
+            assert rp.mask_mesh_count_device(src.request(), stream=src.st) == S.reference("ball").info
+            assert rp.timing_read()[1] == 1 and rp.mmesh_last_kernel_name() == "mmesh_scan_kernel"
+            rp.timing_reset()
+            check(src, "ball", closed=True, normals=True, smooth_iters=5, relax=0.5)
+            assert rp.timing_read()[1] == 1 and rp.mmesh_last_kernel_name() == "mmesh_triangle_kernel"
+            rp.timing_reset()
+            info = vr_amd.vr_mmesh_info()
+            req = src.request()
+            vt, vptr, voff = guarded(VB)
+            tt, tptr, toff = guarded(TB)
+            assert vr_amd.mmesh_lib().vr_mask_mesh_extract_device(rp._ctx, C.byref(req), vptr, 1, tptr, 1, C.byref(info),
+                                                                  src.st) == -28
+            assert rp.timing_read()[1] == 1  # the count pass ran, and its interval is whole
+            rp.timing_enable(False)
+            rp.timing_reset()
+            v, t, hinfo = rp.mask_mesh_extract(a, origin, label, True, True, 5, 0.5)
+            want = S.reference("ball", closed=True, normals=True, smooth_iters=5, relax=0.5)
+            assert rp.timing_read()[1] == 0 and v.tobytes() == want.verts.tobytes() and t.tobytes() == want.tris.tobytes()
         assert src.intact()
     finally:
         rp.close()

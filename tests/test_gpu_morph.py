@@ -16,11 +16,11 @@ import morph_ref as R
 import morph_scenes as S
 import synth
 import vr_amd
+from gpu_kit import GUARD32, device_bytes, ext_of
 from range_scenes import volume
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x77777777
 INF = float("inf")
 AXIS_KERNEL = "morph_edt_axis_kernel<%d, %d>"
 
@@ -32,39 +32,24 @@ def rp(gpu):
     p.close()
 
 
-def ext_of(m):
-    return (m.shape[2], m.shape[1], m.shape[0])
-
-
-def device_mask(m, odd=False):
-    """The mask in device memory (a torch tensor to keep, the pointer); odd: at an odd address."""
-    import torch
-    b = np.frombuffer(np.ascontiguousarray(m).tobytes(), np.uint8)
-    t = torch.full((b.size + 8,), 0x55, dtype=torch.uint8, device="cuda")
-    off = 1 if odd else 0
-    t[off:off + b.size] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + off
-
-
 def edt_device(rp, m, target, odd=False, cap_extra=3):
     import torch
-    keep, ptr = device_mask(m, odd)
-    d = torch.full((m.size + 8,), GUARD, dtype=torch.int32, device="cuda")
+    keep, ptr = device_bytes(m, odd)
+    d = torch.full((m.size + 8,), GUARD32, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
     info = rp.distance_transform_device(ext_of(m), ptr, m.dtype.itemsize, d.data_ptr(), m.size + cap_extra,
                                         to_set=target == R.TO_SET, stream=stream.cuda_stream)
     # (complete on return: no synchronisation of ours before the copy on another stream)
     h = d.cpu().numpy().view(np.uint32)
-    assert np.all(h[m.size:] == GUARD)
+    assert np.all(h[m.size:] == GUARD32)
     assert keep.cpu().numpy()[(1 if odd else 0):][:m.nbytes].tobytes() == m.tobytes()  # the mask is only read
     return h[:m.size].reshape(m.shape), info
 
 
 def morph_device(rp, m, op, r2, odd=False):
     import torch
-    keep, ptr = device_mask(m, odd)
+    keep, ptr = device_bytes(m, odd)
     o = torch.full((m.size + 9,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     stream = torch.cuda.Stream()
@@ -155,8 +140,8 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     m = S.mask("rows129")
     n = m.size
     ext = (C.c_uint32 * 3)(*ext_of(m))
-    keep, mp = device_mask(S.as_labels(m))
-    d = torch.full((n + 4,), GUARD, dtype=torch.int32, device="cuda")
+    keep, mp = device_bytes(S.as_labels(m))
+    d = torch.full((n + 4,), GUARD32, dtype=torch.int32, device="cuda")
     o = torch.full((n + 4,), 0x77, dtype=torch.uint8, device="cuda")
     torch.cuda.synchronize()
     ei, mi = vr_amd.vr_edt_info(), vr_amd.vr_morph_info()
@@ -178,7 +163,7 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     assert (ei.voxels, ei.target_voxels, ei.max_dist2, ei.max_index) == (n, 0, 0, 0)
     assert morph(cap=n - 1) == -28 and (mi.voxels, mi.in_set, mi.out_set) == (n, 0, 0)
     hd = np.zeros(n, np.uint32)
-    hd[:] = GUARD
+    hd[:] = GUARD32
     ho = np.full(n, 0x77, np.uint8)
     assert L.vr_edt_squared(rp._ctx, ext, m.ctypes.data, 1, 0, hd.ctypes.data, n - 1, C.byref(ei)) == -28
     assert L.vr_mask_morph(rp._ctx, ext, 0, 1, m.ctypes.data, 1, ho.ctypes.data, n - 1, C.byref(mi)) == -28
@@ -196,8 +181,8 @@ def test_every_error_leaves_the_outputs_untouched(rp):
     assert bad == [-22] * len(bad), bad
     assert bytes(ei) == b"\x77" * 24 and bytes(mi) == b"\x77" * 24
     torch.cuda.synchronize()
-    assert np.all(d.cpu().numpy().view(np.uint32) == GUARD) and np.all(o.cpu().numpy() == 0x77)
-    assert np.all(hd == GUARD) and np.all(ho == 0x77)
+    assert np.all(d.cpu().numpy().view(np.uint32) == GUARD32) and np.all(o.cpu().numpy() == 0x77)
+    assert np.all(hd == GUARD32) and np.all(ho == 0x77)
     assert keep.cpu().numpy()[:4 * n].tobytes() == S.as_labels(m).tobytes()
     # r2 just below the sentinel is a radius like any other: everything within reach of a set voxel
     assert morph(op=0, r2=0xFFFFFFFE) == 0 and (mi.voxels, mi.out_set) == (n, n)
@@ -237,9 +222,9 @@ def test_region_grow_then_open_and_labels_then_edt(gpu):
         assert dm.cpu().numpy()[:n].tobytes() == want_mask.tobytes()
         # the labels of the window as a 4-byte mask
         nc = linfo["components"]
-        dl = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-        dc = torch.full((nc * 16 + 16,), GUARD, dtype=torch.int32, device="cuda")
-        dd = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
+        dl = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+        dc = torch.full((nc * 16 + 16,), GUARD32, dtype=torch.int32, device="cuda")
+        dd = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
         assert rp.label_device(dl.data_ptr(), n, dc.data_ptr(), nc, lo, hi, 6, None, stream=stream.cuda_stream) == linfo
         for target in (R.TO_SET, R.TO_UNSET):
@@ -247,7 +232,7 @@ def test_region_grow_then_open_and_labels_then_edt(gpu):
                                                 to_set=target == R.TO_SET, stream=stream.cuda_stream)
             want, want_info = R.edt(labels, target)
             h = dd.cpu().numpy().view(np.uint32)
-            assert info == want_info and h[:n].tobytes() == want.tobytes() and np.all(h[n:] == GUARD)
+            assert info == want_info and h[:n].tobytes() == want.tobytes() and np.all(h[n:] == GUARD32)
         # the thickest point of the ball: the largest distance to the outside
         assert info["max_dist2"] >= 25
         assert dl.cpu().numpy().view(np.uint32)[:n].tobytes() == labels.tobytes()

@@ -13,16 +13,12 @@ import pytest
 import mpr_ref
 import synth
 import vr_amd
+from gpu_kit import c_plane
 from mpr_scenes import (CLEAR, FULL, INSET, OPS, PITCH_IN, PITCH_OVER, SLICE, closed_form_expected,
                         closed_form_stack, closed_form_volume, face_size, make_plane, reference, volume)
 from range_scenes import STORAGE, bits, int_volume
 
 pytestmark = pytest.mark.gpu
-
-
-def c_plane(pl):
-    return vr_amd.mpr_plane(pl["origin"], pl["du"], pl["dv"], pl["dn"], pl["width"], pl["height"],
-                            pl["nsamples"], pl["op"])
 
 
 def mpr_pass(vol, tf, box=FULL, w=32, h=24, vrange=None, **kw):

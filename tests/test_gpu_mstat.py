@@ -19,10 +19,11 @@ import mstat_ref as R
 import mstat_scenes as S
 import synth
 import vr_amd
+from gpu_kit import GUARD32, context_untouched, device_bytes, ext_of, unchanged
+from gpu_kit import stream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 0x77777777
 INF = float("inf")
 F = np.float32
 DT = vr_amd.MSTAT_REGION_DTYPE
@@ -40,35 +41,6 @@ def make_pass(vol, layout):
     rp.volume_dataset_changed(synth.dataset(np.asarray(vol).astype(dtype)))
     assert rp.volume_info()[2] == storage
     return rp
-
-
-@pytest.fixture(scope="module")
-def stream(gpu):
-    import torch
-    return torch.cuda.Stream()
-
-
-def ext_of(a):
-    return (a.shape[2], a.shape[1], a.shape[0])
-
-
-def device_bytes(a, odd=False):
-    """The array's bytes in device memory (a tensor to keep, the pointer), 0x55 around them; odd: at
-    an odd address."""
-    import torch
-    b = np.frombuffer(np.ascontiguousarray(a).tobytes(), np.uint8)
-    t = torch.full((b.size + 16,), 0x55, dtype=torch.uint8, device="cuda")
-    off = 1 if odd else 0
-    if b.size:
-        t[off:off + b.size] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + off
-
-
-def unchanged(keep, a, odd=False):
-    h = keep.cpu().numpy()
-    off = 1 if odd else 0
-    return h[off:off + a.nbytes].tobytes() == a.tobytes() and np.all(h[:off] == 0x55) and np.all(h[off + a.nbytes:] == 0x55)
 
 
 def stats_device(rp, stream, mask, origin=(0, 0, 0), hist=None, odd=False):
@@ -258,16 +230,16 @@ def test_the_chain_behind_the_labeller(gpu, stream, box_pass, layout):
     shape = labels.shape
     vol = R.crop(full, box[0], shape)
     assert nc > 8
-    dl = torch.full((n + 8,), GUARD, dtype=torch.int32, device="cuda")
-    dc = torch.full((nc * 16 + 8,), GUARD, dtype=torch.int32, device="cuda")
-    dr = torch.full((nc * 16 + 8,), GUARD, dtype=torch.int32, device="cuda")
+    dl = torch.full((n + 8,), GUARD32, dtype=torch.int32, device="cuda")
+    dc = torch.full((nc * 16 + 8,), GUARD32, dtype=torch.int32, device="cuda")
+    dr = torch.full((nc * 16 + 8,), GUARD32, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     st = stream.cuda_stream
     assert rp.label_device(dl.data_ptr(), n, dc.data_ptr(), nc, lo, hi, 6, box, stream=st) == linfo
     info = rp.label_stats_device(shape[::-1], dl.data_ptr(), dc.data_ptr(), nc, dr.data_ptr(), nc, box[0], stream=st)
     hr = dr.cpu().numpy().view(np.uint32)
     rec = np.frombuffer(hr[:nc * 16].tobytes(), DT)
-    assert np.all(hr[nc * 16:] == GUARD)
+    assert np.all(hr[nc * 16:] == GUARD32)
     assert info == {"voxels": n, "set": linfo["in_voxels"], "unlisted": 0, "regions": nc}
     assert np.array_equal(rec["voxels"], table["voxels"]) and int(rec["voxels"].sum()) == linfo["in_voxels"]
     assert np.array_equal(rec["label"], table["label"])
@@ -462,7 +434,7 @@ def test_every_error_leaves_the_outputs_untouched(gpu, box_pass):
     keep, mp = device_bytes(lab)
     kt, tp = device_bytes(tab)
     o = torch.full((n + 8,), 0x77, dtype=torch.uint8, device="cuda")
-    dr = torch.full((nt * 16 + 4,), GUARD, dtype=torch.int32, device="cuda")
+    dr = torch.full((nt * 16 + 4,), GUARD32, dtype=torch.int32, device="cuda")
     torch.cuda.synchronize()
     reg, mi, wi, hi = vr_amd.vr_mstat_region(), vr_amd.vr_mstat_info(), vr_amd.vr_morph_info(), vr_amd.vr_hist_info()
     bins = np.full(8, 0x7777777777777777, np.uint64)
@@ -521,20 +493,20 @@ def test_every_error_leaves_the_outputs_untouched(gpu, box_pass):
     assert bad == [-22] * len(bad), bad
     assert bytes(reg) == b"\x77" * 64 and bytes(mi) == b"\x77" * 32 and bytes(wi) == b"\x77" * 24 and bytes(hi) == b"\x77" * 40
     torch.cuda.synchronize()
-    assert np.all(o.cpu().numpy() == 0x77) and np.all(dr.cpu().numpy().view(np.uint32) == GUARD)
+    assert np.all(o.cpu().numpy() == 0x77) and np.all(dr.cpu().numpy().view(np.uint32) == GUARD32)
     assert np.all(bins == 0x7777777777777777) and np.all(hr == 0x77) and np.all(ho == 0x77)
     assert unchanged(keep, lab) and unchanged(kt, tab)
     # the grid may end on the volume's last voxel, and an empty table is a table
     assert stats(org=e3(nx - 7, ny - 6, nz - 5)) == 0 and reg.label == 1
     assert labels(ntable=0, rcap=0) == 0 and (mi.voxels, mi.set, mi.unlisted, mi.regions) == (n, int((lab != 0).sum()),
                                                                                                 int((lab != 0).sum()), 0)
-    assert np.all(dr.cpu().numpy().view(np.uint32) == GUARD)
+    assert np.all(dr.cpu().numpy().view(np.uint32) == GUARD32)
     # a table that is not ascending: VR_OK, the guards intact
     rev = np.ascontiguousarray(tab[::-1])
     krev, rp_ = device_bytes(rev)
     assert labels(table=rp_) == 0 and (mi.voxels, mi.set, mi.regions) == (n, int((lab != 0).sum()), nt)
     h = dr.cpu().numpy().view(np.uint32)
-    assert np.all(h[nt * 16:] == GUARD) and unchanged(krev, rev)
+    assert np.all(h[nt * 16:] == GUARD32) and unchanged(krev, rev)
     assert np.array_equal(np.frombuffer(h[:nt * 16].tobytes(), DT)["label"], rev["label"])
     # no volume: a fresh context refuses
     empty = vr_amd.OffscreenPass(16, 16)
@@ -556,34 +528,28 @@ def test_the_calls_leave_the_context_as_it_was(gpu, stream):
     vol = label_scenes.noise()
     rp = hit_scenes.hit_pass(32, 24, np.asarray(vol), synth.tf_color(), 0.5)
     try:
-        cam = synth.camera("rotA").to_vr_camera()
-        p = vr_amd.default_params(shading=1, skip_empty=1)
-        before = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        rep = rp.memory_report()
-        last = rp.last_kernel_name()
-        assert rp.mstat_last_kernel_name() == ""  # a fresh context
-        labels, table, linfo = rp.label(0.7, 1.0, 6)
-        last = rp.last_kernel_name()
-        m = S.byte_mask(vol.shape)
-        rp.timing_enable(True)
-        rp.timing_reset()
-        got = stats_device(rp, stream, m, hist=(16, 0.0, 1.0))
-        assert rp.timing_read()[1] == 1  # each call's passes are one interval
-        assert rp.mstat_last_kernel_name() == "mstat_finalize_kernel<f32>"
-        check_stats(got, R.mask_stats(vol, m, False, (16, 0.0, 1.0)), "state", exact=False, values=vol[m != 0])
-        rp.timing_reset()
-        rec, info = labels_device(rp, stream, labels, table)
-        assert rp.timing_read()[1] == 1 and np.array_equal(rec["voxels"], table["voxels"])
-        rp.timing_reset()
-        out, info = window_device(rp, stream, m, vol.shape, 0.7, 1.0)
-        assert rp.timing_read()[1] == 1 and rp.mstat_last_kernel_name() == "mstat_window_kernel<f32>"
-        assert out.tobytes() == R.window(vol, m, 0.7, 1.0)[0].tobytes()
-        rp.timing_enable(False)
-        rp.timing_reset()
-        rp.mask_stats(m)
-        assert rp.timing_read()[1] == 0
-        assert rp.memory_report() == rep and rp.last_kernel_name() == last
-        assert np.array_equal(rp.render(cam, p, vr_amd.OUT_RGBA32F).view(np.uint32), before.view(np.uint32))
+        with context_untouched(rp) as state:
+            assert rp.mstat_last_kernel_name() == ""  # a fresh context
+            labels, table, linfo = rp.label(0.7, 1.0, 6)
+            state.rebase()  # (the label family's name: the calls after it leave it alone)
+            m = S.byte_mask(vol.shape)
+            rp.timing_enable(True)
+            rp.timing_reset()
+            got = stats_device(rp, stream, m, hist=(16, 0.0, 1.0))
+            assert rp.timing_read()[1] == 1  # each call's passes are one interval
+            assert rp.mstat_last_kernel_name() == "mstat_finalize_kernel<f32>"
+            check_stats(got, R.mask_stats(vol, m, False, (16, 0.0, 1.0)), "state", exact=False, values=vol[m != 0])
+            rp.timing_reset()
+            rec, info = labels_device(rp, stream, labels, table)
+            assert rp.timing_read()[1] == 1 and np.array_equal(rec["voxels"], table["voxels"])
+            rp.timing_reset()
+            out, info = window_device(rp, stream, m, vol.shape, 0.7, 1.0)
+            assert rp.timing_read()[1] == 1 and rp.mstat_last_kernel_name() == "mstat_window_kernel<f32>"
+            assert out.tobytes() == R.window(vol, m, 0.7, 1.0)[0].tobytes()
+            rp.timing_enable(False)
+            rp.timing_reset()
+            rp.mask_stats(m)
+            assert rp.timing_read()[1] == 0
     finally:
         rp.close()
 

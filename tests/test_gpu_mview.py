@@ -19,27 +19,14 @@ import mview_scenes as S
 import pyoracle
 import synth
 import vr_amd
+from gpu_kit import GUARD, c_plane, context_untouched, device_bytes, err, ext_of, guarded, read_guarded, unchanged
+from gpu_kit import stream  # noqa: F401
 from range_scenes import FULL, INSET, SLICE, volume
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
 DT = vr_amd.MVIEW_HIT_DTYPE
-GUARD = 0x77
-
-
-@pytest.fixture(scope="module")
-def stream(gpu):
-    import torch
-    return torch.cuda.Stream()
-
-
-def err(rp):
-    return vr_amd.lib().vr_last_error(rp._ctx).decode()
-
-
-def ext_of(a):
-    return (a.shape[2], a.shape[1], a.shape[0])
 
 
 def make_pass(w, h, vol, box=FULL, **kw):
@@ -48,39 +35,6 @@ def make_pass(w, h, vol, box=FULL, **kw):
     rp.transfer_function_changed(synth.tf_color())
     rp.slicing_changed(*box)
     return rp
-
-
-def device_bytes(a, odd=False):
-    """The array's bytes in device memory (a tensor to keep, the pointer), 0x55 around them; odd: at
-    an odd address (byte masks)."""
-    import torch
-    b = np.frombuffer(np.ascontiguousarray(a).tobytes(), np.uint8)
-    t = torch.full((b.size + 16,), 0x55, dtype=torch.uint8, device="cuda")
-    off = 1 if odd else 0
-    t[off:off + b.size] = torch.from_numpy(b.copy()).cuda()
-    torch.cuda.synchronize()
-    return t, t.data_ptr() + off
-
-
-def unchanged(keep, a, odd=False):
-    h = keep.cpu().numpy()
-    off = 1 if odd else 0
-    return h[off:off + a.nbytes].tobytes() == a.tobytes() and np.all(h[:off] == 0x55) and np.all(h[off + a.nbytes:] == 0x55)
-
-
-def guarded(nbytes):
-    """A device buffer of nbytes at a 4-byte (not 8-byte) aligned address with guard bytes around it."""
-    import torch
-    t = torch.full((nbytes + 24,), GUARD, dtype=torch.uint8, device="cuda")
-    torch.cuda.synchronize()
-    off = 4 if t.data_ptr() % 8 == 0 else 8 - t.data_ptr() % 8 + 4
-    return t, t.data_ptr() + off, off
-
-
-def read_guarded(t, off, nbytes):
-    h = t.cpu().numpy()
-    assert np.all(h[:off] == GUARD) and np.all(h[off + nbytes:] == GUARD)
-    return h[off:off + nbytes].tobytes()
 
 
 class Source:
@@ -282,10 +236,6 @@ def test_all_set_is_vr_hit_entry_and_all_zero_is_its_count(gpu, stream):
         rp.close()
 
 
-def to_vr_plane(pl):
-    return vr_amd.mpr_plane(pl["origin"], pl["du"], pl["dv"], pl["dn"], pl["width"], pl["height"], pl["nsamples"], pl["op"])
-
-
 @pytest.mark.parametrize("dims", E.MPR_VOLUMES, ids=lambda d: "x".join(map(str, d)))
 def test_slices(gpu, stream, dims):
     """edge_shapes' planes: thin, five-sample slabs, oblique and 1 x 1; the FULL and an inset box; ANY
@@ -299,7 +249,7 @@ def test_slices(gpu, stream, dims):
             srcs = {l: Source(rp, stream, a, (0, 0, 0), l) for l in (None, 256)}
             zsrc = Source(rp, stream, zero)
             for name, pl in E.mpr_planes(dims, E.geometry("f32")):
-                vp = to_vr_plane(pl)
+                vp = c_plane(pl)
                 for label, src in srcs.items():
                     wimg, winfo = R.slice_image(dims, a, pl, box, label=label)
                     for occ in (False, True):
@@ -326,7 +276,7 @@ def test_a_slice_of_the_grid_inside_the_volume(gpu, stream):
             wimg, winfo = R.slice_image(S.GRID_VOLUME, a, pl, SLICE, S.GRID_ORIGIN, 65536)
             assert winfo["hits"] >= 10
             for occ in (False, True):
-                got, info = slice_device(rp, stream, to_vr_plane(pl), src, occ)
+                got, info = slice_device(rp, stream, c_plane(pl), src, occ)
                 assert got == wimg.tobytes() and info == winfo
         assert rp.mview_last_kernel_name() == "mview_slice_kernel<u32, occ>"
     finally:
@@ -590,7 +540,7 @@ def test_stale_occupancy_words_stay_inside_the_buffers(gpu, stream):
             torch.cuda.synchronize()
             src.occ, src.occ_ptr = occ, ptr
             got, info = hits_device(rp, stream, cam, p, src, True)
-            sgot, sinfo = slice_device(rp, stream, to_vr_plane(pl), src, True)
+            sgot, sinfo = slice_device(rp, stream, c_plane(pl), src, True)
             assert read_guarded(occ, off, 8) == bytes([fill]) * 8 and src.intact()
             if fill:
                 assert got == want[0].tobytes() and info == want[1]
@@ -609,38 +559,34 @@ def test_the_calls_leave_the_context_as_it_was(gpu, stream):
     try:
         cam = synth.camera("rotA").to_vr_camera()
         p = vr_amd.default_params(shading=1, skip_empty=1)
-        before = rp.render(cam, p, vr_amd.OUT_RGBA32F)
-        rep = rp.memory_report()
-        last = rp.last_kernel_name()
-        assert rp.mview_last_kernel_name() == ""  # a fresh context
-        m = S.byte_mask(ext_of(vol), 0.02)
-        src = Source(rp, stream, m)
-        rp.timing_enable(True)
-        rp.timing_reset()
-        src.build()
-        assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_occupancy_kernel<u8>"
-        rp.timing_reset()
-        got, info = hits_device(rp, stream, cam, p, src, True)
-        assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_hit_kernel<u8, occ>"
-        sc = pyoracle.Scene.from_params(vol, 0.0, 1.0, synth.tf_color(), cam, 32, 24, p)
-        want = R.hit_image(sc, m)
-        assert got == want[0].tobytes() and info == want[1]
-        rp.timing_reset()
-        y, x = np.argwhere(want[0]["step"] != R.MISS)[0]
-        assert rp.mask_pick(cam, p, src.src(), int(x), int(y)).tobytes() == want[0][y, x].tobytes()
-        assert rp.timing_read()[1] == 1
-        rp.timing_reset()
-        pl = mpr_ref.axis_plane(2, 0.5, 19, 17, 3, 0.02)
-        sgot, sinfo = slice_device(rp, stream, to_vr_plane(pl), src, False)
-        assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_slice_kernel<u8>"
-        wimg, winfo = R.slice_image(ext_of(vol), m, pl)
-        assert sgot == wimg.tobytes() and sinfo == winfo
-        rp.timing_enable(False)
-        rp.timing_reset()
-        rec, hinfo = rp.mask_hit_render(cam, p, m)
-        assert rp.timing_read()[1] == 0 and rec.tobytes() == want[0].tobytes()
-        assert rp.memory_report() == rep and rp.last_kernel_name() == last
-        assert np.array_equal(rp.render(cam, p, vr_amd.OUT_RGBA32F).view(np.uint32), before.view(np.uint32))
+        with context_untouched(rp, cam, p):
+            assert rp.mview_last_kernel_name() == ""  # a fresh context
+            m = S.byte_mask(ext_of(vol), 0.02)
+            src = Source(rp, stream, m)
+            rp.timing_enable(True)
+            rp.timing_reset()
+            src.build()
+            assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_occupancy_kernel<u8>"
+            rp.timing_reset()
+            got, info = hits_device(rp, stream, cam, p, src, True)
+            assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_hit_kernel<u8, occ>"
+            sc = pyoracle.Scene.from_params(vol, 0.0, 1.0, synth.tf_color(), cam, 32, 24, p)
+            want = R.hit_image(sc, m)
+            assert got == want[0].tobytes() and info == want[1]
+            rp.timing_reset()
+            y, x = np.argwhere(want[0]["step"] != R.MISS)[0]
+            assert rp.mask_pick(cam, p, src.src(), int(x), int(y)).tobytes() == want[0][y, x].tobytes()
+            assert rp.timing_read()[1] == 1
+            rp.timing_reset()
+            pl = mpr_ref.axis_plane(2, 0.5, 19, 17, 3, 0.02)
+            sgot, sinfo = slice_device(rp, stream, c_plane(pl), src, False)
+            assert rp.timing_read()[1] == 1 and rp.mview_last_kernel_name() == "mview_slice_kernel<u8>"
+            wimg, winfo = R.slice_image(ext_of(vol), m, pl)
+            assert sgot == wimg.tobytes() and sinfo == winfo
+            rp.timing_enable(False)
+            rp.timing_reset()
+            rec, hinfo = rp.mask_hit_render(cam, p, m)
+            assert rp.timing_read()[1] == 0 and rec.tobytes() == want[0].tobytes()
     finally:
         rp.close()
 
@@ -657,9 +603,9 @@ def test_a_multi_device_context_computes_on_its_lowest_device(gpu, stream):
         assert grp.mask_pick(cam, p, src.src(), int(xs[0]), int(ys[0])).tobytes() == want[0][ys[0], xs[0]].tobytes()
         pl = mpr_ref.axis_plane(2, 9.5 / 20, 43, 24, 5, 1.0 / 20)
         wimg, winfo = R.slice_image(S.GRID_VOLUME, wm, pl, SLICE, S.GRID_ORIGIN, 256)
-        got, info = slice_device(grp, stream, to_vr_plane(pl), src, True)
+        got, info = slice_device(grp, stream, c_plane(pl), src, True)
         assert got == wimg.tobytes() and info == winfo
-        img, info = grp.mask_slice(to_vr_plane(pl), wm, S.GRID_ORIGIN, 256)
+        img, info = grp.mask_slice(c_plane(pl), wm, S.GRID_ORIGIN, 256)
         assert img.tobytes() == wimg.tobytes() and info == winfo
         assert grp.mview_last_kernel_name() == "mview_slice_kernel<u32>"
     finally:

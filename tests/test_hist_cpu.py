@@ -13,6 +13,7 @@ import pytest
 
 import hist_ref
 import vr_amd
+from harness import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -219,21 +220,9 @@ int main(void) { printf("%zu %zu %zu %zu %zu %zu %zu  %zu %zu %zu %zu %zu %zu %z
 # ---- the host helper header, stand-alone, under AddressSanitizer + UBSan -----------------------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
 def test_host_helpers_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "hist_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "hist_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "hist_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "hist harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "hist")
     seen = boxes = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] == "box":
             # the request-check table: the box rule and the brick range, restated here (no size bound:

@@ -1,11 +1,10 @@
 """CPU: the hit records (include/vr/vr_hit.h) -- the binding's symbols and structs, the refusals
 that need no device, the C++ shim, the host helper header under AddressSanitizer + UBSan in a
-stand-alone program, the hit_kernel instantiations in the library's code object, and the
+stand-alone program (the hit_kernel instantiations: tests/test_kernel_inventory_cpu.py), and the
 reference helper tests/hit_ref.py pinned independently: its ISO step and cap mask against
 iso_ref, OPACITY against ENTRY and a closed form, MAX's value against proj_ref's MIP pixel.
 No GPU: nothing here creates a context."""
 import ctypes as C
-import itertools
 import os
 import re
 import shutil
@@ -21,15 +20,13 @@ import proj_ref
 import pyoracle
 import synth
 import vr_amd
+from harness import run_sanitized
 from hit_scenes import KEYS, PARITY, THRESHOLDS
 from range_scenes import FULL, H, W, volume
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.dirname(vr_amd.LIB_PATH)
 F = np.float32
-NS = "void vr::(anonymous namespace)::"
-TYPES = ["unsigned char", "signed char", "unsigned short", "short", "float",
-         "vr::Quad8<unsigned char>", "vr::Quad8<signed char>"]
 
 
 # ---- the binding -------------------------------------------------------------------------------------
@@ -142,21 +139,9 @@ int main(int argc, char **)
 # ---- the host helper header, stand-alone, under AddressSanitizer + UBSan -----------------------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
 def test_host_helpers_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "hit_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "hit_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "hit_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "hit harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "hit")
     seen = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "rect":
             continue
@@ -170,35 +155,6 @@ def test_host_helpers_under_sanitizers(tmp_path):
             assert got == ([x0, y0, rw, rh] if use else [0, 0, fw, fh]), line
         seen += 1
     assert seen == 19
-
-
-# ---- the kernels in the library ------------------------------------------------------------------------
-def _demangled_kernels():
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols() if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_hit_kernels_are_exactly_the_expected_105():
-    want = {f"{NS}hit_kernel<{t}, {kind}, {count}, {k}>(vr::MarchParams, vr::HitArgs)"
-            for t, kind, (count, k) in itertools.product(TYPES, range(5), (("false", 1), ("false", 2),
-                                                                             ("true", 1)))}
-    assert len(want) == 7 * 5 * 3 == 105
-    _, dem = _demangled_kernels()
-    built = {d for d in dem if "hit_kernel<" in d}
-    assert built - want == set() and want - built == set()
-    # the name stays out of the other families' matches
-    assert not any(f"::{fam}<" in d for d in built
-                   for fam in ("march_kernel", "mip_kernel", "iso_kernel", "proj_kernel", "mpr_kernel",
-                               "hist_kernel"))
-
-
-def test_every_kernel_that_existed_before_is_still_there():
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_hit.txt")).read().split()
-    assert len(before) == 527 and not any("hit_kernel" in n for n in before)
-    kd, _ = _demangled_kernels()
-    assert set(before) - set(kd) == set()
 
 
 # ---- the reference, pinned independently ---------------------------------------------------------------

@@ -1,8 +1,8 @@
 """CPU: connected components and region growing (include/vr/vr_label.h) -- the reference helper
 tests/label_ref.py pinned against a plain breadth-first search, scipy where it is installed and
 the counts beside the scenes; the binding's symbols and structs; the refusals that need no device;
-the C++ shim; the host helper header under AddressSanitizer + UBSan in a stand-alone program; and
-the label_* kernels in the library's code object.
+the C++ shim; and the host helper header under AddressSanitizer + UBSan in a stand-alone program
+(the label_* kernels: tests/test_kernel_inventory_cpu.py).
 No GPU: nothing here creates a context."""
 import ctypes as C
 import os
@@ -16,12 +16,10 @@ import pytest
 import label_ref
 import label_scenes as S
 import vr_amd
+from harness import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.dirname(vr_amd.LIB_PATH)
-NS = "vr::(anonymous namespace)::"
-TYPES = ["unsigned char", "signed char", "unsigned short", "short", "float",
-         "vr::Quad8<unsigned char>", "vr::Quad8<signed char>"]
 SMALL = [k for k in S.CASES]
 
 
@@ -235,22 +233,10 @@ int main(int argc, char **)
 # ---- the host helper header, stand-alone, under AddressSanitizer + UBSan ---------------------------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
 def test_host_helpers_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "label_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "label_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "label_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "label harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "label")
     # the request-check table: the box rule, the 2^32 - 1 bound and the brick range, restated here
     seen = refused_for_size = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "box":
             continue
@@ -270,37 +256,3 @@ def test_host_helpers_under_sanitizers(tmp_path):
             assert nwork == min(nb[0] * nb[1] * nb[2], 2 ** 64 - 1), line
         seen += 1
     assert seen == 26 and refused_for_size == 7
-
-
-# ---- the kernels in the library ------------------------------------------------------------------------
-def _demangled_kernels():
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols() if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_label_kernels_are_exactly_the_expected_ones():
-    want = {f"void {NS}label_local_kernel<{t}, {c}>(vr::LabelArgs)" for t in TYPES for c in (6, 26)}
-    geoms = ["vr::BrickGeom<8, 8, 8, 0>", "vr::BrickGeom<7, 8, 8, 0>"]  # every layout but plain 8-bit; plain 8-bit
-    want |= {f"void {NS}label_seam_kernel<{c}, {g}>(vr::LabelArgs)" for c in (6, 26) for g in geoms}
-    want |= {f"{NS}label_{k}_kernel(vr::LabelArgs)" for k in ("flatten", "scan_chunks", "table_init", "accum",
-                                                                "largest", "grow")}
-    assert len(want) == 14 + 4 + 6 == 24
-    _, dem = _demangled_kernels()
-    norm = lambda s: s.replace("> >", ">>")
-    built = {norm(d) for d in dem if "label_" in d}
-    assert built - {norm(w) for w in want} == set() and {norm(w) for w in want} - built == set()
-    forbidden = ("mesh_", "march_kernel", "mip_kernel", "iso_kernel", "proj_kernel", "mpr_kernel", "hist_kernel",
-                 "hit_kernel")
-    assert not [d for d in built if any(f in d for f in forbidden)]
-
-
-def test_every_kernel_that_existed_before_is_still_there():
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_label.txt")).read().split()
-    mesh = open(os.path.join(ROOT, "tests", "golden", "kernels_before_mesh.txt")).read().split()
-    assert len(before) == 632 + 30 and not any("label_" in n for n in before)
-    assert set(mesh) < set(before) and all("mesh_" in n for n in set(before) - set(mesh))
-    kd, _ = _demangled_kernels()
-    assert set(before) - set(kd) == set()
-    assert all("label_" in n for n in set(kd) - set(before))

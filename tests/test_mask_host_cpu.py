@@ -2,12 +2,9 @@
 a stand-alone program, tools/host_sanitize/mask_harness.cpp: every reason code at its boundary, a
 refused grid left untouched, and per family the text each reason code maps to -- compared here with
 the literal strings the three family headers held while each stated the rule itself.  No GPU."""
-import os
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from harness import run_sanitized
 
 # MaskReason 1..4: the extent, the voxel count, elem_bytes, the alignment
 TEXTS = {
@@ -34,17 +31,7 @@ REFUSALS = [
 
 @pytest.fixture(scope="module")
 def harness_output(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mask") / "mask_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "mask_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "mask harness ok" in r.stdout and "FAILED" not in r.stdout
-    return r.stdout.splitlines()
+    return run_sanitized(tmp_path_factory.mktemp("mask"), "mask").splitlines()
 
 
 def test_the_grid_rule_at_its_boundaries(harness_output):

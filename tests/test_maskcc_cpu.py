@@ -1,8 +1,8 @@
 """CPU: the components of a mask (include/vr/vr_maskcc.h) -- the reference tests/maskcc_ref.py pinned
 against a breadth-first search and against scipy; the scenes hold what they are for; the third
-library's symbols, structs and kernels; the refusals that need no device; the host helper header
-under AddressSanitizer + UBSan in a stand-alone program; and the first two libraries' kernels,
-which this family leaves alone.  No GPU: nothing here creates a context."""
+library's symbols and structs; the refusals that need no device; and the host helper header
+under AddressSanitizer + UBSan in a stand-alone program (the kernels of every library:
+tests/test_kernel_inventory_cpu.py).  No GPU: nothing here creates a context."""
 import ctypes as C
 import os
 import re
@@ -16,9 +16,9 @@ import label_ref
 import maskcc_ref as R
 import maskcc_scenes as S
 import vr_amd
+from harness import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NS = "vr::(anonymous namespace)::"
 
 
 def structure(connectivity):
@@ -206,22 +206,10 @@ def test_host_helpers_under_sanitizers(tmp_path):
     """Every refusal that needs no device, -22 and -28 alike, and the launch geometry, on
     csrc/vr_maskcc_host.h itself (the library's entry points refuse a NULL context before they
     reach it)."""
-    exe = str(tmp_path / "maskcc_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "maskcc_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "maskcc_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "maskcc harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "maskcc")
     # the grid rule and the geometry, restated here
     seen = refused = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "grid":
             continue
@@ -240,38 +228,3 @@ def test_host_helpers_under_sanitizers(tmp_path):
             assert nbytes == -(-(12 * nwords + 4 * nchunks) // 8) * 8 + 64, line  # about 3/16 byte a voxel
         seen += 1
     assert seen == 37 and refused == 11
-
-
-# ---- the kernels in the three libraries ------------------------------------------------------------------
-def _demangled_kernels(path):
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols(path) if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_maskcc_kernels_are_exactly_the_expected_ones():
-    want = {f"void {NS}mcc_rows_kernel<{eb}, {inv}>(vr::MccArgs, unsigned long)" for eb in (1, 4) for inv in (0, 1)}
-    want |= {f"void {NS}mcc_link_kernel<{conn}>(vr::MccArgs, unsigned long)" for conn in (6, 26)}
-    want |= {f"void {NS}mcc_select_kernel<{fill}>(vr::MccArgs)" for fill in (0, 1)}
-    want |= {f"{NS}mcc_{k}_kernel(vr::MccArgs)" for k in ("flatten", "scan", "table_init", "largest", "keep")}
-    want |= {f"{NS}mcc_accum_kernel(vr::MccArgs, unsigned long)"}
-    assert len(want) == 14
-    kd, dem = _demangled_kernels(vr_amd.MASKCC_LIB_PATH)
-    assert set(dem) == want and len(kd) == 14
-    assert all(f"{NS}mcc_" in d for d in dem)
-    # no existing family's name, and no existing kernel's
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    existing = subprocess.run(["c++filt"], input="\n".join(before), capture_output=True, text=True, check=True).stdout
-    base = set(re.findall(r"::(\w+_kernel)\b", existing)) | {"morph_edt_x_kernel", "morph_edt_axis_kernel"}
-    assert len(base) > 30 and "label_flatten_kernel" in base and "march_kernel" in base
-    forbidden = ("label_", "morph_", "mesh_") + tuple(sorted(base))
-    assert not [d for d in dem if any(f in d for f in forbidden)]
-
-
-def test_the_other_two_libraries_keep_exactly_their_kernels():
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    kd, dem = _demangled_kernels(vr_amd.LIB_PATH)
-    assert kd == sorted(before) and not any("mcc_" in d for d in dem)
-    kd, dem = _demangled_kernels(vr_amd.MORPH_LIB_PATH)
-    assert len(kd) == 8 and all("morph_" in d for d in dem)

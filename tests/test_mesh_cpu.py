@@ -3,8 +3,8 @@ by properties that no implementation detail enters (closedness, orientation, the
 between the mesh's volume and inside_voxels, the tie to the ISO hit records), the binding's symbols
 and structs, the refusals that need no device, the C++ shim, the host helper header and the PLY
 writer under AddressSanitizer + UBSan in a stand-alone program, the PLY writer of the library
-through a reader of the test's own, and the mesh_* kernels in the library's code object.
-No GPU: nothing here creates a context."""
+through a reader of the test's own, and the frame kernels' machine code (the mesh_* kernels:
+tests/test_kernel_inventory_cpu.py).  No GPU: nothing here creates a context."""
 import ctypes as C
 import json
 import os
@@ -20,14 +20,12 @@ import hit_scenes
 import mesh_ref
 import mesh_scenes as S
 import vr_amd
+from harness import run_sanitized
 from range_scenes import volume
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIBDIR = os.path.dirname(vr_amd.LIB_PATH)
 F = np.float32
-NS = "vr::(anonymous namespace)::"
-TYPES = ["unsigned char", "signed char", "unsigned short", "short", "float",
-         "vr::Quad8<unsigned char>", "vr::Quad8<signed char>"]
 CLOSED = [k for k in S.CASES if k[1]]
 
 
@@ -217,22 +215,10 @@ int main(int argc, char **)
 # ---- the host helper header and the PLY writer, stand-alone, under AddressSanitizer + UBSan --------------
 @pytest.mark.skipif(shutil.which("g++") is None, reason="g++ missing")
 def test_host_helpers_under_sanitizers(tmp_path):
-    exe = str(tmp_path / "mesh_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "mesh_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "mesh_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe, str(tmp_path)], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "mesh harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "mesh", args=[str(tmp_path)])
     # the request-check table: the box rule and the cell range, restated here
     seen = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "box":
             continue
@@ -299,33 +285,6 @@ def test_ply_round_trip(tmp_path):
     assert not os.path.exists(none)
     with pytest.raises(RuntimeError, match="cannot write"):
         vr_amd.write_ply(str(tmp_path / "no" / "such" / "dir.ply"), m.verts, m.tris)
-
-
-# ---- the kernels in the library ------------------------------------------------------------------------
-def _demangled_kernels():
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols() if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_mesh_kernels_are_exactly_the_expected_30():
-    want = {f"void {NS}mesh_classify_kernel<{t}>(vr::MeshArgs)" for t in TYPES}
-    want |= {f"void {NS}mesh_quad_kernel<{t}>(vr::MeshArgs)" for t in TYPES}
-    want |= {f"void {NS}mesh_vertex_kernel<{t}, {n}>(vr::MeshArgs)" for t in TYPES for n in ("false", "true")}
-    want |= {f"{NS}mesh_scan_bricks_kernel(vr::MeshArgs)", f"{NS}mesh_scan_chunks_kernel(vr::MeshArgs)"}
-    assert len(want) == 7 * 4 + 2 == 30
-    _, dem = _demangled_kernels()
-    norm = lambda s: s.replace("> >", ">>")
-    built = {norm(d) for d in dem if "mesh_" in d}
-    assert built - {norm(w) for w in want} == set() and {norm(w) for w in want} - built == set()
-
-
-def test_every_kernel_that_existed_before_is_still_there():
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_mesh.txt")).read().split()
-    assert len(before) == 632 and not any("mesh_" in n for n in before)
-    kd, _ = _demangled_kernels()
-    assert set(before) - set(kd) == set()
 
 
 def test_frame_kernels_keep_the_parents_machine_code():

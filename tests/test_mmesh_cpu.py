@@ -20,6 +20,7 @@ import mesh_scenes
 import mmesh_ref as R
 import mmesh_scenes as S
 import vr_amd
+from harness import run_sanitized
 
 ROOT = S.ROOT
 F = np.float32
@@ -235,23 +236,11 @@ def test_host_helpers_under_sanitizers(tmp_path):
     """Every refusal that needs no device at its boundary, with its text, and the geometry and scratch
     sizes up to the largest grids, on csrc/vr_mmesh_host.h itself (the library's entry points refuse a
     NULL context before they reach it)."""
-    exe = str(tmp_path / "mmesh_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "mmesh_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "mmesh_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "mmesh harness ok" in r.stdout and "FAILED" not in r.stdout
-    assert "request rules checked" in r.stdout and "output rules checked" in r.stdout
+    stdout = run_sanitized(tmp_path, "mmesh")
+    assert "request rules checked" in stdout and "output rules checked" in stdout
     # the geometry of every printed grid, restated here (tests/mmesh_scenes.py geometry)
     seen, largest = 0, 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "geom":
             continue
@@ -273,4 +262,4 @@ def test_host_helpers_under_sanitizers(tmp_path):
                 for closed in (0, 1):
                     g = S.geometry((a * 11, b, c), closed)
                     tot = [tot[0] + g["node_words"], tot[1] + g["cell_words"], tot[2] + g["cells"]]
-    assert "totals %d node words %d cell words %d cells" % tuple(tot) in r.stdout
+    assert "totals %d node words %d cell words %d cells" % tuple(tot) in stdout

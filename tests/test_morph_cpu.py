@@ -1,8 +1,8 @@
 """CPU: the exact distance transform and ball morphology (include/vr/vr_morph.h) -- the reference
 tests/morph_ref.py pinned against the definitions pair by pair and against scipy where it is
-installed; the second library's symbols and structs; the refusals that need no device; the host
-helper header under AddressSanitizer + UBSan in a stand-alone program; the morph_* kernels in the
-second library's code object, and the first library's kernels, which this family leaves alone.
+installed; the second library's symbols and structs; the refusals that need no device; and the host
+helper header under AddressSanitizer + UBSan in a stand-alone program (the kernels of both
+libraries: tests/test_kernel_inventory_cpu.py).
 No GPU: nothing here creates a context."""
 import ctypes as C
 import os
@@ -16,9 +16,9 @@ import pytest
 import morph_ref as R
 import morph_scenes as S
 import vr_amd
+from harness import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NS = "vr::(anonymous namespace)::"
 
 
 # ---- the reference, pinned before anything is compared with it ----------------------------------------
@@ -180,22 +180,10 @@ def test_argument_errors_without_a_device():
 def test_host_helpers_under_sanitizers(tmp_path):
     """Every refusal that needs no device, -22 and -28 alike, on csrc/vr_morph_host.h itself (the
     library's entry points refuse a NULL context before they reach it)."""
-    exe = str(tmp_path / "morph_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "morph_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "morph_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "morph harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "morph")
     # the grid rule and the tiling, restated here
     seen = refused = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "grid":
             continue
@@ -215,34 +203,3 @@ def test_host_helpers_under_sanitizers(tmp_path):
                 assert tiles == slabs * -(-line_len // wd), line
         seen += 1
     assert seen == 31 and refused == 11
-
-
-# ---- the kernels in the two libraries --------------------------------------------------------------------
-def _demangled_kernels(path):
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols(path) if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_morph_kernels_are_exactly_the_expected_ones():
-    want = {f"void {NS}morph_edt_x_kernel<{eb}>(vr::MorphArgs, unsigned long)" for eb in (1, 4)}
-    want |= {f"void {NS}morph_edt_axis_kernel<{fin}, {words}>(vr::MorphArgs, vr::MorphAxis)"
-             for fin in (0, 1, 2) for words in (16384, 32768)}
-    assert len(want) == 8
-    kd, dem = _demangled_kernels(vr_amd.MORPH_LIB_PATH)
-    assert set(dem) == want and len(kd) == 8
-    assert all("morph_" in d for d in dem)
-    forbidden = ("label_", "mesh_", "march_kernel", "mip_kernel", "iso_kernel", "proj_kernel", "mpr_kernel",
-                 "hist_kernel", "hit_kernel")
-    assert not [d for d in dem if any(f in d for f in forbidden)]
-
-
-def test_the_first_library_keeps_exactly_its_kernels():
-    """A kernel family now lives in a library of its own: libvr_amd.so's kernel list is the parent's."""
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    label = open(os.path.join(ROOT, "tests", "golden", "kernels_before_label.txt")).read().split()
-    assert len(before) == 662 + 24 and set(label) < set(before)
-    assert all("label_" in n for n in set(before) - set(label)) and not any("morph_" in n for n in before)
-    kd, _ = _demangled_kernels(vr_amd.LIB_PATH)
-    assert kd == sorted(before)

@@ -24,7 +24,7 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def c_plane(pl):
+def ref_plane(pl):
     """The C helper's plane as mpr_ref's dict."""
     return mpr_ref.plane(list(pl.origin), list(pl.du), list(pl.dv), list(pl.dn), pl.width, pl.height,
                          pl.nsamples, pl.op)
@@ -44,7 +44,7 @@ def test_thin_axis_slices_show_exactly_one_voxel(axis, k):
     want = closed_form_expected(vol, axis, k)
     assert want.shape == (h, w)
     for op in OPS.values():
-        pl = c_plane(vr_amd.axis_plane(axis, (k + 0.5) / n, w, h, 1, 0.0, op))
+        pl = ref_plane(vr_amd.axis_plane(axis, (k + 0.5) / n, w, h, 1, 0.0, op))
         img, st = mpr_ref.render(vol, lo, hi, tf, pl)
         assert st == dict(rays=w * h, steps=w * h, samples=w * h)
         for py in range(h):
@@ -72,7 +72,7 @@ def test_slabs_of_texel_centres_reduce_the_voxel_stack(axis, k, half):
         acc = acc + layer
     want = {"max": np.fmax.reduce(stack), "min": np.fmin.reduce(stack), "mean": acc / F(ns)}
     for opname, op in OPS.items():
-        pl = c_plane(vr_amd.axis_plane(axis, (k + 0.5) / n, w, h, ns, 1.0 / n, op))
+        pl = ref_plane(vr_amd.axis_plane(axis, (k + 0.5) / n, w, h, ns, 1.0 / n, op))
         img, st = mpr_ref.render(vol, lo, hi, tf, pl)
         assert st == dict(rays=w * h, steps=w * h * ns, samples=w * h * ns)
         exp = np.array([[mpr_ref.pixel_of(want[opname][py, px], lo, hi, tf) for px in range(w)]
@@ -100,7 +100,7 @@ def test_nan_rules_of_the_helper():
     tf = synth.tf_color()
     imgs = {}
     for opname, op in OPS.items():
-        pl = c_plane(vr_amd.axis_plane(2, 13.5 / 32, 16, 8, 3, 1.0 / 32, op))
+        pl = ref_plane(vr_amd.axis_plane(2, 13.5 / 32, 16, 8, 3, 1.0 / 32, op))
         imgs[opname] = mpr_ref.render(vol, lo, hi, tf, pl)[0]
     # the filter's weight-0 lerp fmaf(0, b - a, a) is NaN when the upper neighbour b is: the sample
     # at z = 12 reads the NaN at z + 1 = 13, so of the pixel's three samples only z = 14 is a number

@@ -1,8 +1,8 @@
 """CPU: the volume under a mask or a label array (include/vr/vr_mstat.h) -- the reference
 tests/mstat_ref.py pinned against a voxel-by-voxel restatement, np.bincount and scipy.ndimage; the
-scenes hold what they are for; the fourth library's symbols, structs and kernels; the refusals that
-need no device; the host helper header under AddressSanitizer + UBSan in a stand-alone program; and
-the other three libraries' kernels, which this family leaves alone.  No GPU: nothing here creates a
+scenes hold what they are for; the fourth library's symbols and structs; the refusals that
+need no device; and the host helper header under AddressSanitizer + UBSan in a stand-alone program
+(the kernels of every library: tests/test_kernel_inventory_cpu.py).  No GPU: nothing here creates a
 context."""
 import ctypes as C
 import math
@@ -22,9 +22,9 @@ import label_scenes
 import mstat_ref as R
 import mstat_scenes as S
 import vr_amd
+from harness import run_sanitized
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NS = "vr::(anonymous namespace)::"
 F = np.float32
 
 
@@ -296,24 +296,12 @@ def test_host_helpers_under_sanitizers(tmp_path):
     """Every refusal that needs no device, -22 and -28 alike, the launch geometry and the brick
     addressing the kernels share, on csrc/vr_mstat_host.h itself (the library's entry points refuse a
     NULL context before they reach it)."""
-    exe = str(tmp_path / "mstat_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "mstat_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "mstat_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "mstat harness ok" in r.stdout and "FAILED" not in r.stdout
+    stdout = run_sanitized(tmp_path, "mstat")
     # the four geometries over the extents 1 .. 15 per axis: (1 + .. + 15)^3 voxels each
-    assert f"addressing {4 * 120 ** 3} voxels" in r.stdout
+    assert f"addressing {4 * 120 ** 3} voxels" in stdout
     # the grid rule and the geometry, restated here
     seen = refused = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "grid":
             continue
@@ -331,42 +319,3 @@ def test_host_helpers_under_sanitizers(tmp_path):
             assert nbytes == 64 + 4096 * 12 + nrec * 116, line  # 48 KiB and 116 bytes a record
         seen += 1
     assert seen == 38 and refused == 11
-
-
-# ---- the kernels in the four libraries -------------------------------------------------------------------
-def _demangled_kernels(path):
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols(path) if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_mstat_kernels_are_exactly_the_expected_ones():
-    types = [("float", 0), ("unsigned short", 1), ("short", 1), ("unsigned char", 2), ("signed char", 2),
-             ("unsigned char", 3), ("signed char", 3)]  # the seven base layouts: (element type, geometry)
-    tail = "(vr::MstatArgs, unsigned int, unsigned int, unsigned long)"
-    want = {f"void {NS}mstat_mask_kernel<{t}, {k}, {h}>{tail}" for t, k in types for h in ("true", "false")}
-    want |= {f"void {NS}mstat_labels_kernel<{t}, {k}>{tail}" for t, k in types}
-    want |= {f"void {NS}mstat_window_kernel<{t}, {k}>{tail}" for t, k in types}
-    want |= {f"void {NS}mstat_finalize_kernel<{f}>(vr::MstatArgs)" for f in ("true", "false")}
-    want |= {f"{NS}mstat_gather_kernel(vr::MstatArgs)"}
-    assert len(want) == 31
-    kd, dem = _demangled_kernels(vr_amd.MSTAT_LIB_PATH)
-    assert set(dem) == want and len(kd) == 31
-    assert all(f"{NS}mstat_" in d for d in dem)
-    # no existing kernel's name
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    existing = subprocess.run(["c++filt"], input="\n".join(before), capture_output=True, text=True, check=True).stdout
-    base = set(re.findall(r"::(\w+_kernel)\b", existing))
-    assert len(base) > 30 and "hist_kernel" in base
-    assert not [d for d in dem if any(f"::{b}" in d for b in base) or "mcc_" in d or "morph_" in d]
-
-
-def test_the_other_three_libraries_keep_exactly_their_kernels():
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    kd, dem = _demangled_kernels(vr_amd.LIB_PATH)
-    assert kd == sorted(before) and not any("mstat_" in d for d in dem)
-    kd, dem = _demangled_kernels(vr_amd.MORPH_LIB_PATH)
-    assert len(kd) == 8 and all("morph_" in d for d in dem)
-    kd, dem = _demangled_kernels(vr_amd.MASKCC_LIB_PATH)
-    assert len(kd) == 14 and all("mcc_" in d for d in dem)

@@ -1,8 +1,8 @@
 """CPU: the view of a mask or a label array (include/vr/vr_mview.h) -- the reference tests/mview_ref.py
 pinned against hit_ref's ENTRY records and MAX counters, closed-form normals and a voxel-by-voxel
-occupancy; the scenes hold what they are for; the fifth library's symbols, structs and kernels (none
-of which uses scratch memory); the refusals that need no device; and the host helper header under
-AddressSanitizer + UBSan in a stand-alone program.  No GPU: nothing here creates a context."""
+occupancy; the scenes hold what they are for; the fifth library's symbols and structs; the refusals
+that need no device; and the host helper header under AddressSanitizer + UBSan in a stand-alone
+program (the kernels and their scratch memory: tests/test_kernel_inventory_cpu.py).  No GPU: nothing here creates a context."""
 import ctypes as C
 import os
 import re
@@ -17,10 +17,10 @@ import mpr_ref
 import mview_ref as R
 import mview_scenes as S
 import vr_amd
+from harness import run_sanitized
 from range_scenes import FULL, volume
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NS = "vr::(anonymous namespace)::"
 F = np.float32
 
 
@@ -283,23 +283,11 @@ def test_host_helpers_under_sanitizers(tmp_path):
     """Every refusal that needs no device at its boundary, with its text, vr_mview_occupancy_words and
     the cell geometry of every grid of 1 .. 20 voxels per axis, on csrc/vr_mview_host.h itself (the
     library's entry points refuse a NULL context before they reach it)."""
-    exe = str(tmp_path / "mview_harness")
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                        "-fno-omit-frame-pointer",
-                        os.path.join(ROOT, "tools", "host_sanitize", "mview_harness.cpp"), "-o", exe],
-                       capture_output=True, text=True)
-    if r.returncode != 0 and "sanitize" in r.stderr and "mview_harness.cpp" not in r.stderr:
-        pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
-    assert r.returncode == 0, r.stderr[-3000:]
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
-               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=120)
-    assert r.returncode == 0 and "runtime error" not in r.stderr, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "mview harness ok" in r.stdout and "FAILED" not in r.stdout
-    assert "source rules checked" in r.stdout and "call rules checked" in r.stdout
+    stdout = run_sanitized(tmp_path, "mview")
+    assert "source rules checked" in stdout and "call rules checked" in stdout
     # the word counts and the geometry totals, restated here
     seen = 0
-    for line in r.stdout.splitlines():
+    for line in stdout.splitlines():
         w = line.replace(":", " ").split()
         if w[0] != "words":
             continue
@@ -312,54 +300,4 @@ def test_host_helpers_under_sanitizers(tmp_path):
     n = range(1, 21)
     cells = sum(-(-a // 8) * -(-b // 8) * -(-c // 8) for a in n for b in n for c in n)
     words = sum(-(-(-(-a // 8) * -(-b // 8) * -(-c // 8)) // 32) for a in n for b in n for c in n)
-    assert f"geometry {210 ** 3} voxels {cells} cells {words} words" in r.stdout
-
-
-# ---- the kernels in the five libraries -------------------------------------------------------------------
-def _demangled_kernels(path):
-    kd = sorted(name[:-3].decode() for name, _ in vr_amd.code_object_symbols(path) if name.endswith(b".kd"))
-    dem = subprocess.run(["c++filt"], input="\n".join(kd), capture_output=True, text=True,
-                         check=True).stdout.split("\n")
-    return kd, [d for d in dem if d]
-
-
-def test_mview_kernels_are_exactly_the_expected_ones():
-    elems = ("unsigned char", "unsigned int")
-    want = {f"void {NS}mview_occupancy_kernel<{t}>(vr::MviewOccArgs)" for t in elems}
-    want |= {f"void {NS}mview_hit_kernel<{t}, {o}>(vr::MarchParams, vr::MviewHitArgs)" for t in elems for o in ("true", "false")}
-    want |= {f"void {NS}mview_slice_kernel<{t}, {o}>(vr::MviewSliceArgs)" for t in elems for o in ("true", "false")}
-    assert len(want) == 10
-    kd, dem = _demangled_kernels(vr_amd.MVIEW_LIB_PATH)
-    assert set(dem) == want and len(kd) == 10  # the pick is a hit kernel: no fourth body
-    assert all(f"{NS}mview_" in d for d in dem)
-    # no existing kernel's name
-    before = open(os.path.join(ROOT, "tests", "golden", "kernels_before_morph.txt")).read().split()
-    existing = subprocess.run(["c++filt"], input="\n".join(before), capture_output=True, text=True, check=True).stdout
-    base = set(re.findall(r"::(\w+_kernel)\b", existing))
-    assert len(base) > 30 and "hit_kernel" in base and "mpr_kernel" in base
-    assert not [d for d in dem if any(f"::{b}<" in d or f"::{b}(" in d for b in base) or "mcc_" in d or "morph_" in d
-                or "mstat_" in d]
-    # and the other four libraries keep theirs
-    kd, dem = _demangled_kernels(vr_amd.LIB_PATH)
-    assert kd == sorted(before) and not any("mview_" in d for d in dem)
-    for path, n, tag in ((vr_amd.MORPH_LIB_PATH, 8, "morph_"), (vr_amd.MASKCC_LIB_PATH, 14, "mcc_"),
-                         (vr_amd.MSTAT_LIB_PATH, 31, "mstat_")):
-        kd, dem = _demangled_kernels(path)
-        assert len(kd) == n and all(tag in d for d in dem)
-
-
-@pytest.mark.skipif(not os.path.exists(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")), reason="hipcc missing")
-def test_no_kernel_uses_scratch_memory(tmp_path):
-    """The compiler's resource-usage remarks of the kernel unit, compiled with the Makefile's flags."""
-    mk = open(os.path.join(ROOT, "volumetric-renderer_amd", "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS = (.*?\\\n.*?)$", mk, re.M).group(1).replace("\\\n", " ")
-    flags = flags.replace("$(ARCH)", "gfx950").replace("$(EXTRA)", "").split()
-    r = subprocess.run([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + flags +
-                       ["-c", os.path.join(ROOT, "volumetric-renderer_amd", "csrc", "vr_mview_kernels.hip"),
-                        "-o", str(tmp_path / "mview.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == 10 and all("mview_" in n for n in names), names
-    assert scratch == [0] * 10, dict(zip(names, scratch))
+    assert f"geometry {210 ** 3} voxels {cells} cells {words} words" in stdout

@@ -11,17 +11,9 @@
 #include <vector>
 
 #include "../../volumetric-renderer_amd/csrc/vr_hist_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static uint32_t bits(float f)
 {
@@ -215,6 +207,5 @@ int main()
         CHECK(!hist_window(one.data(), 16, 0, 1, 0, 1, &a, &b));  // N == 0
         CHECK(a == 0 && b == 0);
     }
-    std::printf(g_bad ? "hist harness: %d FAILED\n" : "hist harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("hist");
 }

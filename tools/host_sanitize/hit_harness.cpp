@@ -11,17 +11,9 @@
 
 #include "../../include/vr/vr_hit.h"
 #include "../../volumetric-renderer_amd/csrc/vr_hit_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_hit_request) == 28, "vr_hit_request is 28 bytes");
 static_assert(sizeof(vr_hit) == kHitRecordBytes && kHitRecordBytes == 24, "vr_hit is 24 bytes");
@@ -97,6 +89,5 @@ int main()
         CHECK(hit_pick_resolve(44, 34, 45, 35, &r) == nullptr);
         CHECK(r.x0 == 44 && r.y0 == 34 && r.w == 1 && r.h == 1 && hit_bytes(r) == 24);
     }
-    std::printf(g_bad ? "hit harness: %d FAILED\n" : "hit harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("hit");
 }

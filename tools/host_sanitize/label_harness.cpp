@@ -11,17 +11,9 @@
 
 #include "../../include/vr/vr_label.h"
 #include "../../volumetric-renderer_amd/csrc/vr_label_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_label_request) == 40, "vr_label_request is 40 bytes");
 static_assert(sizeof(vr_label_component) == kLabelComponentBytes && kLabelComponentBytes == 64,
@@ -143,6 +135,5 @@ int main()
         const uint32_t lo[3] = {1, 0, 0};
         box_case(1, lo, line2, line2);      // (2^32 - 2) * 2
     }
-    std::printf(g_bad ? "label harness: %d FAILED\n" : "label harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("label");
 }

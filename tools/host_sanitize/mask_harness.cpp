@@ -10,17 +10,9 @@
 #include "../../volumetric-renderer_amd/csrc/vr_maskcc_host.h"
 #include "../../volumetric-renderer_amd/csrc/vr_morph_host.h"
 #include "../../volumetric-renderer_amd/csrc/vr_mstat_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(kMaskMaxExtent == 32768 && kMaskMaxVoxels == 0xFFFFFFFFull, "the two bounds");
 static_assert(kMaskOk == 0 && kMaskEinval == -22 && kMaskEnospc == -28, "codes");
@@ -145,6 +137,5 @@ int main()
         CHECK(mstat_check_labels(ext, org, mask, tab, 5, mask + 8, 5, &info, true, &g, &m) == kMaskEinval && m);
         std::printf("refusal label_stats_labels -22 %s\n", m ? m : "");
     }
-    std::printf(g_bad ? "mask harness: %d FAILED\n" : "mask harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("mask");
 }

@@ -10,17 +10,9 @@
 
 #include "../../include/vr/vr_maskcc.h"
 #include "../../volumetric-renderer_amd/csrc/vr_maskcc_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_mask_select_request) == 32 && sizeof(vr_mask_select_info) == 40, "vr_maskcc.h structs");
 static_assert(sizeof(vr_label_component) == kMccRecordBytes && sizeof(vr_label_info) == 40, "vr_label.h structs");
@@ -169,6 +161,5 @@ int main()
         const uint32_t last[3] = {3, 2, 1};
         CHECK(mcc_linear(g, last) == 23);
     }
-    std::printf(g_bad ? "maskcc harness: %d FAILED\n" : "maskcc harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("maskcc");
 }

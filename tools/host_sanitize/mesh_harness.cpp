@@ -13,17 +13,9 @@
 
 #include "../../include/vr/vr_mesh.h"
 #include "../../volumetric-renderer_amd/csrc/vr_mesh_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_mesh_request) == 40, "vr_mesh_request is 40 bytes");
 static_assert(sizeof(vr_mesh_vertex) == kMeshVertexBytes && kMeshVertexBytes == 24, "vr_mesh_vertex is 24 bytes");
@@ -174,6 +166,5 @@ int main(int argc, char **argv)
         CHECK(slurp(none).empty());
         CHECK(mesh_write_ply((dir + "/no/such/dir/x.ply").c_str(), v.data(), 4, t.data(), 1, scale, offset, &m) == -1);
     }
-    std::printf(g_bad ? "mesh harness: %d FAILED\n" : "mesh harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("mesh");
 }

@@ -12,17 +12,9 @@
 
 #include "../../include/vr/vr_mmesh.h"
 #include "../../volumetric-renderer_amd/csrc/vr_mmesh_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_mmesh_request) == sizeof(MmeshRequest) && sizeof(vr_mmesh_request) == 64 &&
                   offsetof(vr_mmesh_request, relax) == offsetof(MmeshRequest, relax) &&
@@ -265,10 +257,5 @@ int main()
     request_rules();
     output_rules();
     geometry();
-    if (g_bad) {
-        std::printf("mmesh harness FAILED: %d\n", g_bad);
-        return 1;
-    }
-    std::printf("mmesh harness ok\n");
-    return 0;
+    return harness_done("mmesh");
 }

@@ -9,17 +9,9 @@
 
 #include "../../include/vr/vr_morph.h"
 #include "../../volumetric-renderer_amd/csrc/vr_morph_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_edt_info) == 24 && sizeof(vr_morph_info) == 24, "vr_morph.h infos are 24 bytes");
 static_assert(VR_EDT_NONE == kMorphNone && VR_MORPH_MAX_EXTENT == kMaskMaxExtent, "vr_morph.h constants");
@@ -148,6 +140,5 @@ int main()
         CHECK(morph_check_morph(bad, 2, 1, mask, 1, out, 24, &mi, true, &g, &msg) == -22 && untouched());
         CHECK(morph_check_morph(ext, 2, 1, mask, 1, out, 23, &mi, true, &g, &msg) == -28 && g.voxels == 24);
     }
-    std::printf(g_bad ? "morph harness: %d FAILED\n" : "morph harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("morph");
 }

@@ -12,17 +12,9 @@
 
 #include "../../include/vr/vr_mstat.h"
 #include "../../volumetric-renderer_amd/csrc/vr_mstat_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_mstat_region) == 64 && sizeof(vr_mstat_info) == 32, "vr_mstat.h structs");
 static_assert(sizeof(vr_mstat_region) == kMstatRecordBytes && sizeof(vr_label_component) == kMstatRecordBytes, "records");
@@ -280,6 +272,5 @@ int main()
         CHECK(window(ext, org, mask, 1, 0.0f, 1.0f, out, 23, &wi, true) == -28 && g.voxels == 24 && msg);
         CHECK(window(ext, org, nullptr, 1, 0.0f, 1.0f, out, 0, &wi, true) == -28 && g.voxels == 24);
     }
-    std::printf(g_bad ? "mstat harness: %d FAILED\n" : "mstat harness ok\n", g_bad);
-    return g_bad ? 1 : 0;
+    return harness_done("mstat");
 }

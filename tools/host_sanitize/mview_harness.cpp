@@ -13,17 +13,9 @@
 
 #include "../../include/vr/vr_mview.h"
 #include "../../volumetric-renderer_amd/csrc/vr_mview_host.h"
+#include "harness_check.h"
 
 using namespace vr;
-
-static int g_bad = 0;
-#define CHECK(x)                                                  \
-    do {                                                          \
-        if (!(x)) {                                               \
-            std::printf("FAILED line %d: %s\n", __LINE__, #x);    \
-            ++g_bad;                                              \
-        }                                                         \
-    } while (0)
 
 static_assert(sizeof(vr_mask_hit) == 32 && sizeof(vr_mview_info) == 48 && sizeof(vr_mview_occ_info) == 32, "structs");
 static_assert(sizeof(vr_mview_source) == sizeof(MviewSource) && offsetof(vr_mview_source, array) == offsetof(MviewSource, array) &&
@@ -292,10 +284,5 @@ int main()
     words_of(37, 19, 17);
     CHECK(mview_occupancy_words(nullptr) == 0);
     geometry();
-    if (g_bad) {
-        std::printf("%d checks FAILED\n", g_bad);
-        return 1;
-    }
-    std::printf("mview harness ok\n");
-    return 0;
+    return harness_done("mview");
 }

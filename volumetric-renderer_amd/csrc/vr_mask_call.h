@@ -1,4 +1,4 @@
-// vr_mask_call.h — private to csrc/vr_api_{morph,maskcc,mstat,mview}.hip: what the entry points of the mask
+// vr_mask_call.h — private to csrc/vr_api_{morph,maskcc,mstat,mview,mmesh}.hip: what the entry points of the mask
 // families share on top of vr_ctx.h -- the skeleton of an entry point with an info struct
 // (mask_call), the host forms' staging of their arrays in device memory (MaskStage) and the
 // family's last kernel name.  The request checks it runs are vr_mask_host.h's and the family's.
